@@ -19,10 +19,16 @@ device (sg_wait_stream); every timed step pushes one resharded slice and reshard
 the engine works on it.
 
 The roofline object prices the NFA advance kernel with the algorithmic byte model of DESIGN.md
- over its HIP-event-timed duration.  cpu_baseline times the CPU oracle (the
-single-threaded restatement of the reference engine) on a bounded prefix of the same stream.
-At N=1 `other_configs` adds BASELINE configs[2] (C3, counting + logical sequence) and configs[3]
-(C4, absent state, playback clock) on the general device engine.
+ over its HIP-event-timed duration in the timed steps.
+
+A plain run does only that: set up, warm up, time the steps, print the line.  `--dump-outputs DIR`
+also writes the matches of the last timed step (what the caller of that step receives) as
+DIR/<name>.npy.  Everything else is behind `--full`: the same launches one batch at a time
+(`stages_ms_isolated`), cpu_baseline (the CPU oracle, the single-threaded restatement of the
+reference engine, on a bounded prefix of the same stream), at N=1 `other_configs` (BASELINE
+configs[2] C3, counting + logical sequence, and configs[3] C4, absent state, playback clock, on the
+general device engine; the Zipf and random-walk C2 variants), the PCIe-, output-, fan-out- and
+API-inclusive legs, at N>1 the host timestamp-order merge leg, and the full record beside the line.
 """
 import argparse
 import importlib
@@ -628,6 +634,23 @@ def take_all(eng, ready):
             return
 
 
+DUMP_ROWS = 1 << 20   # --dump-outputs: 56 B per match as float64 columns, so < 64 MB over all ranks
+
+
+def dump_outputs(path, m, rank, world):
+    """--dump-outputs: the matches of the last timed step (a host Matches, in the engine's order) as
+    float64 arrays path/<name>.npy (ranks > 0: <name>_rank<r>.npy): n_matches (their number), then
+    trigger_seq, key, ts, slot_seq, chain_len — all of them, or when there are more than the size bound
+    allows a fixed seeded sample of rows (ascending row indices, the same for the same number of matches)"""
+    os.makedirs(path, exist_ok=True)
+    n, cap = len(m), DUMP_ROWS // world
+    idx = np.sort(np.random.default_rng(0).choice(n, cap, replace=False)) if n > cap else slice(None)
+    sfx = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(path, f"n_matches{sfx}.npy"), np.array([n], dtype=np.float64))
+    for name in ("trigger_seq", "key", "ts", "slot_seq", "chain_len"):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), getattr(m, name)[idx].astype(np.float64))
+
+
 def pcie_inclusive(sa, synth, torch, dev, cq, n_keys, batch, steps):
     """C2 with the batches handed over in HOST memory (sg_batch.mem = SG_MEM_HOST, pinned buffers):
     the engine's H2D copies of ts / key / the filtered column are inside the timed region.  Reported
@@ -1088,11 +1111,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1 << 24)
     ap.add_argument("--keys", type=int, default=None, help="keys per GPU (default: 2^20 at N=1 (C2), 2^23 at N>1 (C5))")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the matches of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (isolated stages, CPU baselines, other "
+                         "configs, inclusive legs, N > 1: the host merge) and write the full record")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / C4 lines")
-    ap.add_argument("--legs", default=None, help="comma-separated subset of the other legs to run (experiments)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 / C4 lines")
+    ap.add_argument("--legs", default=None,
+                    help="with --full: comma-separated subset of the other legs to run (experiments)")
     args = ap.parse_args()
+    extra, cpu = args.full and not args.no_extra, args.full and not args.no_cpu
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1131,21 +1161,24 @@ def main():
     # inputs resident in HBM before timing: this rank's slice of every step of the global
     # arrival-ordered stream over world * K keys (events per ms scale with the job)
     total = args.warmup + args.steps
-    batches = []
+    batches = {}
     # N > 1: one extra slice, so that every timed step also reshards the NEXT step's slice (below);
-    # N = 1: ISO more steps after the timed region, run one at a time (the kernels alone on the GPU)
-    ISO = 3
-    # N > 1: MERGE more slices for the host timestamp-order merge leg after the timed region (merge_leg)
-    MERGE = 0 if os.environ.get("SG_BENCH_NO_MERGE") else 4
-    for s in range(total + (1 + MERGE if world > 1 else ISO)):
-        base = s * world * B + rank * B
-        # generated on the device, bit-identical to synth.stock_ticks (tests/test_synth.py)
-        t = synth.stock_ticks_torch(torch, base, B, K * world, dev, rate_per_ms=2000 * world)
-        if world > 1:
-            del t["symbol"]
-        batches.append(t)
-    torch.cuda.synchronize()
-    local_seq = [0]
+    # N = 1, --full: ISO more steps after the timed region, run one at a time (the kernels alone on the GPU)
+    ISO = 3 if args.full and world == 1 else 0
+    # N > 1, --full: MERGE more slices for the host timestamp-order merge leg after the timed region (merge_leg)
+    MERGE = 4 if args.full and world > 1 and not os.environ.get("SG_BENCH_NO_MERGE") else 0
+    look = 1 if world > 1 else 0
+    n_slices = total + (look + MERGE if world > 1 else ISO)
+    # the slices stay resident while they fit in half of the free HBM (the default run: all of them, generated
+    # before the first step); a longer run holds a window of them and refills it between timed segments
+    # (SG_BENCH_WINDOW: a test hook that sets the window)
+    window = int(os.environ.get("SG_BENCH_WINDOW", 0)) or \
+        max(8, torch.cuda.mem_get_info(dev)[0] // 2 // (B * (24 if world == 1 else 20))) - look
+    if dist:   # one window for all ranks: their segments meet at barriers
+        w = torch.tensor([window], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
+        dist.all_reduce(w, op=dist.ReduceOp.MIN)
+        window = int(w.item())
+    local_seq, step_base = [0], [0]
     import ctypes as C
     lib.sg_wait_stream.argtypes = [C.c_void_p, C.c_void_p]
 
@@ -1154,9 +1187,32 @@ def main():
         t = batches[s]
         return rs({"key": t["key"], "ts": t["ts"], "price": t["price"], "volume": t["volume"]})
 
+    def resident(s, end):
+        """slices [s, e) (and the look-ahead slice) resident, e = min(end, s + window); returns e.  Slices below s
+        are dropped once the engine has finished with them"""
+        e = min(end, s + window)
+        if all(i in batches for i in range(s, min(e + look, n_slices))):
+            return e
+        if batches:
+            drain()
+            for i in [i for i in batches if i < s]:
+                del batches[i]
+        for i in range(s, min(s + window + look, n_slices)):
+            if i in batches:
+                continue
+            base = i * world * B + rank * B
+            # generated on the device, bit-identical to synth.stock_ticks (tests/test_synth.py)
+            t = synth.stock_ticks_torch(torch, base, B, K * world, dev, rate_per_ms=2000 * world)
+            if world > 1:
+                del t["symbol"]
+            batches[i] = t
+        torch.cuda.synchronize()
+        return e
+
+    resident(0, n_slices)
     nxt = [reshard_step(0) if world > 1 else None]
 
-    def step(s, sink=None):
+    def step(s, sink=None, ready=True):
         if world > 1:
             g = nxt[0]
             # the engine's stream waits for the exchange on the device (no host synchronisation)
@@ -1170,6 +1226,7 @@ def main():
             n = B
             cols = (B, t["ts"].data_ptr(), [t["symbol"].data_ptr(), t["price"].data_ptr(), t["volume"].data_ptr()],
                     t["key"].data_ptr())
+        step_base[0] = local_seq[0]
         eng.push(0, local_seq[0], cols, [0, 1, 2], mem=sa.native.SG_MEM_DEVICE)
         local_seq[0] += n
         if world > 1:
@@ -1184,43 +1241,73 @@ def main():
         else:
             # pipelined: the matches of the batches already complete; batch s's grouping runs while
             # batch s-1 advances (the engine's two streams), no host round trip between batches
-            take_all(eng, True)
+            # (ready=False: the step leaves its matches to the drain that follows it)
+            if ready:
+                take_all(eng, True)
 
-    def drain():   # the matches of the batches still in flight
+    kept = {}   # --dump-outputs: the last timed step's matches on the host, the seconds their copy took
+
+    def drain(keep=False):   # the matches of the batches still in flight
         eng.synchronize()
+        if keep and "m" not in kept:
+            # every batch is complete: the clock stops while the pending matches are copied to the host, and
+            # those of the last step (trigger seqs from its first event on) are kept
+            t = time.perf_counter()
+            m = eng.poll()
+            a = int(np.searchsorted(m.trigger_seq, np.uint64(step_base[0])))
+            kept["m"] = type(m)(m.trigger_seq[a:], m.key[a:], m.ts[a:], m.slot_seq[a:], m.chain_len[a:])
+            kept["s"] = time.perf_counter() - t
         take_all(eng, False)
 
-    for s in range(args.warmup):
-        step(s)
+    s = 0
+    while s < args.warmup:
+        e = resident(s, args.warmup)
+        for i in range(s, e):
+            step(i)
+        s = e
     drain()
     st0 = eng.stats()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for s in range(args.warmup, total):
-        step(s)
-    drain()
-    torch.cuda.synchronize()
-    if dist:
-        dist.barrier()
-    t1 = time.perf_counter()
+    # the timed steps, in one segment when their slices are all resident (else the clock runs over each
+    # segment's steps and drain, and stops while the next segment's slices are generated)
+    dump = args.dump_outputs is not None
+    el = 0.0
+    while s < total:
+        e = resident(s, total)
+        if dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(s, e):
+            if dump and i == total - 1:   # its matches go to the host copy in the drain, none to a ready poll
+                step(i, (lambda: drain(True)) if world > 1 else None, ready=False)
+            else:
+                step(i)
+        drain(dump and e == total)
+        torch.cuda.synchronize()
+        if dist:
+            dist.barrier()
+        el += time.perf_counter() - t0
+        s = e
+    el -= kept.get("s", 0.0)
     st1 = eng.stats()
-    el = t1 - t0
+    if "m" in kept:
+        dump_outputs(args.dump_outputs, kept["m"], rank, world)
     if dist:
         tt = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     dst = delta(st0, st1)
     iso = None
-    if world == 1:   # the same kernels without the two-stream overlap (each launch alone on the GPU)
+    if ISO:   # the same kernels without the two-stream overlap (each launch alone on the GPU)
+        resident(total, total + ISO)
         sti0 = eng.stats()
         for s in range(total, total + ISO):
             step(s)
             drain()
         iso = delta(sti0, eng.stats())
     merge = None
-    if world > 1 and MERGE:
+    if MERGE:
+        resident(total, total + MERGE)
         merge = merge_leg(sa, lib, eng, step, total, MERGE, rank, world, dist, dev, B, torch, 2 * maxb)
     if rs is not None:
         rs.check()   # a destination block overflow would have dropped events: the run is invalid
@@ -1286,7 +1373,7 @@ def main():
     torch.cuda.empty_cache()
     if rank == 0:
         progress(f"C2: {out['value']:.3e} events/s ({out['ms_per_step']:.3f} ms per step)")
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and extra:
         steps = max(3, args.steps // 4)
         cb = 1 << 22
         # name: (query, batch maker, keys, batch events, warm-up batches, partial capacity, playback, extra bytes
@@ -1327,7 +1414,7 @@ def main():
                 continue
             r = dict(run_general(sa, synth, torch, dev, q, mk, keys, bsz, 16 if name == "C4_deep_state" else steps,
                                  warm, cap, playback=pb, extra_in=extra, label=name), workload=wl)
-            if not args.no_cpu:
+            if cpu:
                 r["cpu_baseline"] = cpu_general(sa, q, mk, keys, bsz, warm, pb, args.cpu_seconds / 3, name)
             out["other_configs"][name] = r
             progress(f"{name}: {r['value']:.3e} events/s")
@@ -1335,15 +1422,15 @@ def main():
             ds = out["other_configs"]["C4_deep_state"]["roofline"]["counters_per_step"]
             out["other_configs"]["C4_deep_state"]["live_per_touched_key_at_batch_start"] = \
                 ds["live_at_batch_start"] / max(1.0, ds["keys_touched"])
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and extra:
         # SURVEY §8(d) workload variants of the headline config
         for kind in ("zipf", "walk"):
             if args.legs and "C2_" + kind not in args.legs.split(","):
                 continue
             out.setdefault("other_configs", {})["C2_" + kind] = c2_variant(
-                sa, synth, torch, dev, kind, K, B, max(4, args.steps // 8), 3, args.cpu_seconds / 3, args.no_cpu)
+                sa, synth, torch, dev, kind, K, B, max(4, args.steps // 8), 3, args.cpu_seconds / 3, not cpu)
             progress(f"C2_{kind}: {out['other_configs']['C2_' + kind]['value']:.3e} events/s")
-    if rank == 0 and world == 1 and not args.no_extra and not args.legs:
+    if rank == 0 and world == 1 and extra and not args.legs:
         out["pcie_inclusive"] = pcie_inclusive(sa, synth, torch, dev, cq, K, B, 4)
         out["output_inclusive"] = output_inclusive(sa, synth, torch, dev, K, B, 6)
         progress("pcie / output legs done")
@@ -1354,10 +1441,10 @@ def main():
         out["api_columnar"] = api_columnar(sa, synth, 1 << 20, 1 << 20, 8)
         out["api_columnar_cat"] = api_columnar(sa, synth, 1 << 20, 1 << 20, 8, strings="categorical")
         progress("API legs done")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and cpu:
         out["cpu_baseline"] = cpu_baseline(sa, synth, K, B, args.cpu_seconds)
     if rank == 0:
-        print(compact_line(out, write_detail(out, rank)), flush=True)
+        print(compact_line(out, write_detail(out, rank) if args.full else None), flush=True)
     if dist:
         dist.destroy_process_group()
 

@@ -56,7 +56,8 @@ def test_bench_two_rank_rehearsal_with_host_merge():
     env = dict(os.environ, SG_BENCH_DEVICE="0", SG_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", "29519", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--keys", "4096", "--batch", str(1 << 16), "--no-cpu", "--no-extra"]
+           "--steps", "2", "--warmup", "1", "--keys", "4096", "--batch", str(1 << 16), "--full", "--no-cpu",
+           "--no-extra"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

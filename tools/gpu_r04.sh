@@ -20,11 +20,11 @@ tail -2 gpurun_out/gpu_tests_$TAG.log
 echo "== smoke $(date +%T)"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 echo "== bench $(date +%T)"
-timeout -k 10 600 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -30 gpurun_out/bench_$TAG.err; exit 1; }
-tail -c 400 gpurun_out/bench_$TAG.json
+mkdir -p bench_out; timeout -k 10 600 python bench.py --full > bench_out/bench_$TAG.json 2> bench_out/bench_$TAG.err || { tail -30 bench_out/bench_$TAG.err; exit 1; }
+tail -c 400 bench_out/bench_$TAG.json
 [[ "$2" == "skip-prof" ]] && exit 0
 echo "== prof $(date +%T)"
 export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv \
-    -- python3 bench.py --steps 5 --warmup 2 --no-cpu > gpurun_out/prof_$TAG.log 2>&1 || { tail -30 gpurun_out/prof_$TAG.log; exit 1; }
+    -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu > bench_out/prof_$TAG.log 2>&1 || { tail -30 bench_out/prof_$TAG.log; exit 1; }
 find gpurun_out/prof_$TAG -name '*kernel_stats.csv' | head -3
