@@ -70,6 +70,10 @@ __host__ __device__ inline size_t gen_at(uint32_t K, uint32_t blockWords, uint32
 // StateEvent CHN_R, events below min(64, SECAP)), so its next load skips the shape checks; the general kernel clears
 // the mark when it takes the key over
 #define GEN_W0_CHN 0x400u
+// GEN_W0_SEQP (with GEN_W0_REG): seq_kernels.hip keeps two carry records per key and this bit says which one is
+// current (set: record 1).  k_seq_keys flips it for the keys a batch touches, so the batch kernel's threads read the
+// old record while the thread of the run's last event writes the new one
+#define GEN_W0_SEQP 0x800u
 // a deep-store record in 32-bit words: ts[L] i64, seq[L] u64, null bits[L], attribute words[NW][L], queue[Q] i64
 struct GenDeepLayout {
     uint32_t oTs, oSeq, oNb, oW, oQ, words;
@@ -97,6 +101,14 @@ __host__ __device__ inline uint32_t gen_rec_q(uint32_t NW) {
     return r + (r & 1u);
 }
 __host__ __device__ inline uint32_t gen_rec_words(uint32_t NW, uint32_t Q) { return gen_rec_q(NW) + 2u * Q; }
+
+// seq_kernels.hip: rows of one carry record of an n-state sequence (row 0: events held | liveness bits << 4, then
+// per held event, newest first: seq lo, hi, ts lo, hi, null bits, NW words); a key has two (GEN_W0_SEQP), record c's
+// row r of key k at (c * rows + r) * K + k
+__host__ __device__ inline uint32_t seq_rec_rows(uint32_t NW, uint32_t n) { return 1u + (n - 1u) * (5u + NW); }
+#define SEQ_MAXT 4       // seq_kernels.hip: AND-ed terms of one filter
+#define SEQ_NOKEY 0xffffffffu   // GenBatch.ekey: an event of a key handed to the general kernel
+#define SEQ_KEYMASK 0x1fffffffu // GenBatch.ekey: key | record read << 29 | min(rank in the key's run, 3) << 30
 
 enum { GK_STREAM = 0, GK_COUNT = 1, GK_LOGICAL = 2 };
 
@@ -193,6 +205,16 @@ struct GenProgram {
     uint32_t chnKeepW[2], chnKeepA[2];
     int32_t chnAttrK[GEN_MAXA];
     int32_t chnSlotEv[GEN_MAXSLOT];
+    // the stream-state sequence `every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]` (SEQUENCE, partitioned, one
+    // stream, 2 <= n <= 4), which runs on the stencil kernel of seq_kernels.hip (gen_host.hip seq_shape): seqP[i] the
+    // processor of state i, seqSlotEv[s] the state whose event slot s holds; filter i as seqNT[i] AND-ed terms, each
+    // a program at most two entries deep (code[seqTpc, +seqTlen)) with its decoded compare (seqFF.on) when it is one
+    int32_t seqOk, seqN;
+    int32_t seqP[4];
+    int32_t seqSlotEv[GEN_MAXSLOT];
+    int32_t seqNT[4];
+    uint32_t seqTpc[4][SEQ_MAXT], seqTlen[4][SEQ_MAXT];
+    JoFast seqFF[4][SEQ_MAXT];
 };
 #define CHN_MAXN 4       // chn_kernels.hip: states of a chain
 #define CHN_MAXNW 4      // chn_kernels.hip CHN_NW: attribute words of a chained-state stream's event
@@ -259,6 +281,9 @@ struct GenBatch {
     const uint32_t* tile_lo;
     const uint32_t* tpay;
     uint32_t* tileMax;
+    // seq_kernels.hip: per element of the key-sorted batch its key, which carry record the batch reads and its rank
+    // in the key's run (k_seq_keys writes it; SEQ_NOKEY: the general kernel walks the key)
+    uint32_t* ekey;
 };
 
 struct GenOut {

@@ -79,6 +79,16 @@ static const AbsKernel kChnBatch[CHN_MAXN - 1][3] = {{k_chn_batch_1_0, k_chn_bat
 static const AbsKernel kChnWide[CHN_MAXN - 1][3] = {{k_chn_wide_1_0, k_chn_wide_1_1, k_chn_wide_1_2},
                                                     {k_chn_wide_2_0, k_chn_wide_2_1, k_chn_wide_2_2},
                                                     {k_chn_wide_3_0, k_chn_wide_3_1, k_chn_wide_3_2}};
+// [n - 2][attribute words]: the sequence stencil kernels (seq_kernels.hip), their per-key kernels by attribute words
+#define SEQ_DECL(NW) extern "C" __global__ void k_seq_batch_2_##NW(const GenArgs ap); \
+    extern "C" __global__ void k_seq_batch_3_##NW(const GenArgs ap); extern "C" __global__ void k_seq_batch_4_##NW(const GenArgs ap); \
+    extern "C" __global__ void k_seq_keys_##NW(const GenArgs ap); extern "C" __global__ void k_seq_flush_##NW(const GenArgs ap);
+SEQ_DECL(1) SEQ_DECL(2) SEQ_DECL(3) SEQ_DECL(4)
+static const AbsKernel kSeqBatch[3][CHN_MAXNW + 1] = {{nullptr, k_seq_batch_2_1, k_seq_batch_2_2, k_seq_batch_2_3, k_seq_batch_2_4},
+                                                      {nullptr, k_seq_batch_3_1, k_seq_batch_3_2, k_seq_batch_3_3, k_seq_batch_3_4},
+                                                      {nullptr, k_seq_batch_4_1, k_seq_batch_4_2, k_seq_batch_4_3, k_seq_batch_4_4}};
+static const AbsKernel kSeqKeys[CHN_MAXNW + 1] = {nullptr, k_seq_keys_1, k_seq_keys_2, k_seq_keys_3, k_seq_keys_4};
+static const AbsKernel kSeqFlush[CHN_MAXNW + 1] = {nullptr, k_seq_flush_1, k_seq_flush_2, k_seq_flush_3, k_seq_flush_4};
 #define ABSF_DECL(NW) extern "C" __global__ void k_abs_flush_##NW(const GenArgs ap);
 ABSF_DECL(1) ABSF_DECL(2) ABSF_DECL(3) ABSF_DECL(4) ABSF_DECL(5) ABSF_DECL(6) ABSF_DECL(7) ABSF_DECL(8)
 static const AbsKernel kAbsFlush[ABS_MAXNW + 1] = {nullptr, k_abs_flush_1, k_abs_flush_2, k_abs_flush_3, k_abs_flush_4,
@@ -580,6 +590,98 @@ JoFast jo_fast_decode(const uint32_t* code, uint32_t pc, uint32_t n) {
     return f;
 }
 
+// the AND-ed terms of a filter program (postfix `X Y AND`, AndConditionExpressionExecutor is never null, so the
+// filter passes exactly when every term is a non-null true), each at most two entries deep: what seq_kernels.hip
+// evaluates without a stack.  false: the program has a deeper term or ifThenElse.
+static bool seq_terms(const GenProgram& G, uint32_t pc, uint32_t n, std::vector<std::pair<uint32_t, uint32_t>>& out) {
+    if (n == 0) return true;
+    std::vector<uint32_t> at;
+    std::vector<int> dep;
+    int sp = 0;
+    for (uint32_t p = pc; p < pc + n;) {
+        const uint32_t op = G.code[p] & 0xffu;
+        switch (op) {
+        case SG_OP_VAR: case SG_OP_CONST: case SG_OP_ISNULL_EV: sp++; break;
+        case SG_OP_CVT: case SG_OP_NOT: case SG_OP_ISNULL: break;
+        case SG_OP_IFELSE: return false;
+        default: sp--;
+        }
+        at.push_back(p);
+        dep.push_back(sp);
+        p += (uint32_t)sg_op_len(op);
+    }
+    const size_t L = at.size();
+    if (L >= 3 && (G.code[at[L - 1]] & 0xffu) == SG_OP_AND) {
+        size_t j = L - 2;   // X ends at the last instruction before Y's that leaves one entry
+        while (j-- > 0)
+            if (dep[j] == 1) break;
+        if (j >= L - 2) return false;
+        return seq_terms(G, pc, at[j + 1] - pc, out) && seq_terms(G, at[j + 1], at[L - 1] - at[j + 1], out);
+    }
+    const int d = prog_depth(G.code, pc, n);
+    if (d < 0 || d > 2) return false;
+    out.emplace_back(pc, n);
+    return true;
+}
+
+// the stream-state sequence shape of seq_kernels.hip:
+//     every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]      (SEQUENCE, partitioned, one stream, 2 <= n <= 4)
+// with the processors wired as StateInputStreamParser wires that query (chn_shape's checks: each state's post
+// processor feeding the next state's addState, the last one's reaching the selector, `every` around e1 only, no
+// timers, single-event slots, `within` keyed on e1).  The whole event travels in the payload, so the filters may read
+// any attribute of any earlier state.  Anything else stays on the general kernels, the sequence without `every` too.
+void seq_shape(GenProgram& G) {
+    G.seqOk = 0;
+    const int n = G.nprocs;
+    if (G.qtype != SG_Q_SEQUENCE || !G.partitioned || G.nstreams != 1 || n < 2 || n > 4 || G.nslots != n ||
+        G.nStartup != 0 || G.MC != 1 || G.nAll != n || G.nReset != n || G.nUpdate != n)
+        return;
+    const GenRecv& R = G.recv[0];
+    if (R.n != n || R.nStateProcs != n || !R.multi) return;
+    for (int s = 0; s < GEN_MAXSLOT; s++) G.seqSlotEv[s] = -1;
+    for (int i = 0; i < n; i++) {
+        const int p = R.procs[i];
+        if (p < 0 || p >= n) return;
+        const GenPre& P = G.pre[p];
+        const GenPost& Q = G.post[p];
+        if (P.kind != GK_STREAM || P.absent || P.isStart != (i == 0) ||
+            !(P.withinEvery == GEN_NONE || (i == 0 && P.withinEvery == p)))
+            return;
+        if (Q.callbackPre != GEN_NONE || P.thisPost != p) return;
+        if (i + 1 < n) {
+            if (Q.nextStatePre != R.procs[i + 1] || Q.hasNext) return;
+        } else if (Q.nextStatePre != GEN_NONE || !Q.hasNext) {
+            return;
+        }
+        if (Q.nextEveryStatePre != (i == 0 ? p : GEN_NONE)) return;
+        if (P.stateId < 0 || P.stateId >= n || G.slotStream[P.stateId] != 0 || G.seqSlotEv[P.stateId] != -1) return;
+        G.seqSlotEv[P.stateId] = i;
+        G.seqP[i] = p;
+    }
+    if (G.within != -1 && (G.nStartIds != 1 || G.startIds[0] != G.pre[G.seqP[0]].stateId)) return;
+    if (!reg_layout(G) || G.absNW > CHN_MAXNW) return;
+    // (the flushed form: a partial per state over its own events, and the clone)
+    if (G.L < 1u || G.STCAP < 4u || G.SECAP < 6u) return;
+    for (int i = 0; i < n; i++) {
+        const GenPre& P = G.pre[G.seqP[i]];
+        for (uint32_t pc = P.fpc, end = P.fpc + P.flen; pc < end;) {
+            const uint32_t op = G.code[pc] & 0xffu;
+            if (op == SG_OP_VAR && G.code[pc + 1] >= (uint32_t)G.nattr[0]) return;
+            pc += (uint32_t)sg_op_len(op);
+        }
+        std::vector<std::pair<uint32_t, uint32_t>> terms;
+        if (!seq_terms(G, P.fpc, P.flen, terms) || terms.size() > SEQ_MAXT) return;
+        G.seqNT[i] = (int32_t)terms.size();
+        for (size_t q = 0; q < terms.size(); q++) {
+            G.seqTpc[i][q] = terms[q].first;
+            G.seqTlen[i][q] = terms[q].second;
+            G.seqFF[i][q] = jo_fast_decode(G.code, terms[q].first, terms[q].second);
+        }
+    }
+    G.seqN = n;
+    G.seqOk = getenv("SG_NO_SEQ") ? 0 : 1;  // (SG_NO_SEQ: A/B timing against the general kernels; same results)
+}
+
 void abs_shape(GenProgram& G) {
     G.absOk = 0;
     if (G.qtype != SG_Q_PATTERN || !G.partitioned || !G.playback || G.nstreams != 1 || G.nprocs != 2 || G.nslots != 2)
@@ -686,6 +788,7 @@ GenProgram* gen_build_program(const uint32_t* w, size_t nw, uint32_t partialCap)
         abs_shape(*G);
         cnt_shape(*G);
         chn_shape(*G);
+        seq_shape(*G);
         return G;
     } catch (...) {
         delete G;
@@ -1007,8 +1110,10 @@ __global__ void k_gen_live(const GenProgram* G, const uint32_t* S, uint32_t K, u
     unsigned long long live = 0;
     const uint32_t w0 = S[gen_at(K, G->blockWords, G->offST, k, 0)];
     if ((w0 & GEN_W0_REG) && rec) {   // the state in its record (GEN_W0_REG)
-        const uint32_t h = rec[k];
-        if (G->cntOk)   // the count partial: one StateEvent in each list it is in
+        const uint32_t h = rec[(size_t)((G->seqOk && (w0 & GEN_W0_SEQP)) ? seq_rec_rows(G->absNW, G->seqN) : 0u) * K + k];
+        if (G->seqOk)   // the sequence's carry: a partial per set liveness bit
+            live = (unsigned long long)__popc((h >> 4) & 7u);
+        else if (G->cntOk)   // the count partial: one StateEvent in each list it is in
             live = (h & 15u) ? ((h >> 4) & 1u) + ((h >> 5) & 1u) + 2u * ((h >> 6) & 1u) : 0u;
         else            // the absent shape: each partial holds its e1 (the seed holds no event)
             live = h & 15u;
@@ -1045,7 +1150,14 @@ __global__ void k_gen_min_seq(const GenProgram* G, const uint32_t* S, uint32_t K
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long m = ~0ull;
     const uint32_t w0 = k < K ? S[gen_at(K, G->blockWords, G->offST, k, 0)] : 0u;
-    if ((w0 & GEN_W0_REG) && rec) {   // the state in its record (GEN_W0_REG): the events of its partials
+    if ((w0 & GEN_W0_REG) && rec && G->seqOk) {   // the sequence's carry: the first event of its longest partial
+        const size_t base = (size_t)((w0 & GEN_W0_SEQP) ? seq_rec_rows(G->absNW, G->seqN) : 0u);
+        const uint32_t bits = (rec[base * K + k] >> 4) & 7u;
+        if (bits) {
+            const size_t o = (base + 1u + (size_t)(31 - __clz((int)bits)) * (5u + G->absNW)) * K + k;
+            m = (unsigned long long)rec[o] | ((unsigned long long)rec[o + K] << 32);
+        }
+    } else if ((w0 & GEN_W0_REG) && rec) {   // the state in its record (GEN_W0_REG): the events of its partials
         const uint32_t n = rec[k] & 15u, ew = 5u + G->absNW;
         for (uint32_t j = 0; j < n && j < GEN_REC_R; j++) {
             const size_t o = (size_t)(GEN_REC_EV + j * ew) * K + k;
@@ -1298,6 +1410,7 @@ struct GenEngine {
     uint32_t *fb2_list = nullptr, *fb2_start = nullptr;  // the wave-per-key kernels' hand-over (absd_kernels.hip)
     uint32_t* deep = nullptr;                             // their deep store (GEN_W0_DEEP): deepWords per key
     uint32_t deepWords = 0;
+    uint32_t* ekey = nullptr;  // the sequence kernel's per-element tags (GenBatch.ekey)
     uint32_t* rec = nullptr;   // the register-window kernels' records (GEN_W0_REG): gen_rec_words rows per key
     bool absd_nochunk = false; // SG_NO_ABSD_CHUNK: the wave-per-key batch walk event by event
     bool abs_occ4 = true;      // the occupancy-4 absent kernels where they fit (SG_NO_ABS_OCC4: never)
@@ -1500,7 +1613,7 @@ GenEngine* gen_create(const uint32_t* ir, size_t nw, const sg_config& cfg, hipSt
             }
         }
         e->live = e->dalloc<unsigned long long>(1);
-        if (G.absOk || G.cntOk || G.chnOk) {
+        if (G.absOk || G.cntOk || G.chnOk || G.seqOk) {
             e->fb_list = e->dalloc<uint32_t>(K);
             e->fb_start = e->dalloc<uint32_t>(K);
             e->fb_n = e->dalloc<unsigned long long>(1);
@@ -1530,8 +1643,10 @@ GenEngine* gen_create(const uint32_t* ir, size_t nw, const sg_config& cfg, hipSt
                     e->deep = e->dalloc<uint32_t>((size_t)dl.words * K);
                 }
             }
-            const uint64_t rw = gen_rec_words(G.absNW, G.cntOk ? 0u : G.Q);
-            const bool regKernels = G.cntOk || (G.playback && G.partitioned && G.nStartup == 1 && e->keyorder);
+            // (the sequence kernel: its pair of carry records per key, and a tag per batch element)
+            const uint64_t rw = G.seqOk ? 2ull * seq_rec_rows(G.absNW, (uint32_t)G.seqN) : gen_rec_words(G.absNW, G.cntOk ? 0u : G.Q);
+            if (G.seqOk) e->ekey = e->dalloc<uint32_t>(B);
+            const bool regKernels = G.cntOk || G.seqOk || (G.playback && G.partitioned && G.nStartup == 1 && e->keyorder);
             if (regKernels && !getenv("SG_NO_REC") && rw * 4 * K <= (64ull << 30)) {
                 // the register-window kernels' records (GEN_W0_REG): a key's window coalesced across the wave's
                 // keys, written back only where it changed (SG_NO_REC: the blocks, rewritten per touch)
@@ -1546,7 +1661,8 @@ GenEngine* gen_create(const uint32_t* ir, size_t nw, const sg_config& cfg, hipSt
                 e->tile_max = e->dalloc<uint32_t>(1);
                 GH_OK(hipMemsetAsync(e->tile_max, 0, 4, stream));
             }
-            e->wstats = e->dalloc<unsigned long long>((size_t)((K + 63) / 64) * GST_N);
+            // (a row per one-wave workgroup of the per-key kernels, per workgroup of the sequence kernel's batch)
+            e->wstats = e->dalloc<unsigned long long>(std::max<size_t>((K + 63) / 64, G.seqOk ? B / 252 + 2 : 0) * GST_N);
             if (G.playback && G.partitioned && G.nStartup == 1) {
                 e->tstage = e->dalloc<unsigned long long>((size_t)K * ABS_R * 2);
                 e->tm.tstage = e->tstage;
@@ -1590,9 +1706,9 @@ static size_t type_size(int t) {
     }
 }
 
-// the kernels take GenArgs (608 B) by value in their kernel arguments
+// the kernels take GenArgs (616 B) by value in their kernel arguments
 enum { GEN_L_BATCH = 0, GEN_L_TIMERS = 1, GEN_L_DEADLINES = 2, GEN_L_ABS_BATCH = 3, GEN_L_ABS_TIMERS = 4, GEN_L_CNT_BATCH = 5,
-       GEN_L_ABSD_BATCH = 6, GEN_L_ABSD_TIMERS = 7, GEN_L_CHN_BATCH = 8, GEN_L_CHN_WIDE = 9 };
+       GEN_L_ABSD_BATCH = 6, GEN_L_ABSD_TIMERS = 7, GEN_L_CHN_BATCH = 8, GEN_L_CHN_WIDE = 9, GEN_L_SEQ_BATCH = 10 };
 // the general kernels over the keys a register-window kernel handed over: a fixed grid striding the list
 #define GEN_FB_BLOCKS 1024u
 // timer sweeps: a fixed grid of one-wave blocks striding over the due keys (their number is on the device)
@@ -1624,9 +1740,14 @@ static bool absd_on(const GenEngine* e) { return e->fb2_list && absd_lds(e) <= 6
 static bool cnt_on(const GenEngine* e) { return e->host.cntOk && e->host.projN == 0 && e->fb_list; }
 // the chain kernel of chn_kernels.hip runs this query (the shape, no device projection)
 static bool chn_on(const GenEngine* e) { return e->host.chnOk && e->host.projN == 0 && e->fb_list; }
+// the stencil kernel of seq_kernels.hip runs this query (the shape, no device projection, its records; key ids fit
+// the element tags)
+static bool seq_on(const GenEngine* e) {
+    return e->host.seqOk && e->host.projN == 0 && e->fb_list && e->rec && e->ekey && e->K < SEQ_KEYMASK;
+}
 static bool chn_wide_on(const GenEngine* e) { return chn_on(e) && e->host.chnWide && e->fb2_list; }
 // the kernels that read the key-sorted payload with every attribute word of the event
-static bool pay_on(const GenEngine* e) { return abs_on(e) || cnt_on(e) || chn_on(e); }
+static bool pay_on(const GenEngine* e) { return abs_on(e) || cnt_on(e) || chn_on(e) || seq_on(e); }
 
 // both filters of the absent-tail shape are decoded compares (GenPre.ff): the kernel variants without the interpreter
 static bool abs_ff(const GenEngine* e) {
@@ -1657,6 +1778,15 @@ static void launch_gen(GenEngine* e, GenArgs a, int which) {
         hipLaunchKernelGGL(kChnBatch[e->host.chnN - 2][e->host.chnKW], dim3(blocks), dim3(64), 0, e->stream, ap);
         hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((blocks + 1023) / 1024, 16u)), dim3(256),
                            0, e->stream, e->wstats, blocks, e->stats);
+    }
+    else if (which == GEN_L_SEQ_BATCH) {
+        // one lane per key (adopt / hand over, the element tags), one thread per element with an n - 1 halo per
+        // workgroup, then the workgroups' counter rows
+        const uint32_t NW = e->host.absNW, T = 256u - ((uint32_t)e->host.seqN - 1u), wg = (a.b.n + T - 1u) / T;
+        hipLaunchKernelGGL(kSeqKeys[NW], dim3(blocks), dim3(64), 0, e->stream, ap);
+        hipLaunchKernelGGL(kSeqBatch[e->host.seqN - 2][NW], dim3(wg), dim3(256), 0, e->stream, ap);
+        hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((wg + 1023) / 1024, 16u)), dim3(256), 0,
+                           e->stream, e->wstats, wg, e->stats);
     }
     else if (which == GEN_L_CHN_WIDE) {   // a fixed grid striding the hand-over list (its length is on the device)
         const uint32_t wb = std::min<uint32_t>(GEN_FB_BLOCKS, blocks);
@@ -1885,6 +2015,15 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
         a.fb_start = e->fb_start;
         a.mode = GEN_M_TFIRST;   // (this shape emits at most one match per event)
         launch_gen(e, a, GEN_L_CNT_BATCH);
+        a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
+    } else if (seq_on(e)) {
+        // the stencil kernel, then the general kernel over the keys whose state it could not adopt (whole runs)
+        a.fb_list = e->fb_list;
+        a.fb_n = e->fb_n;
+        a.fb_start = e->fb_start;
+        a.b.ekey = e->ekey;
+        a.mode = GEN_M_TFIRST;   // (this shape emits at most one match per event)
+        launch_gen(e, a, GEN_L_SEQ_BATCH);
         a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
     } else if (chn_on(e)) {
         // the chain kernel, then the general kernel over the keys it handed over (from the event where each stopped)
@@ -2344,6 +2483,9 @@ std::string gen_describe(const GenEngine* e) {
         adv += " + k_gen_timers (keys handed over)";
     } else if (cnt_on(e)) {
         push = "k_cnt_batch_" + nw + " (register window, lane per key) + k_gen_batch (keys handed over)";
+    } else if (seq_on(e)) {
+        push = "k_seq_keys_" + nw + " (lane per key) + k_seq_batch_" + std::to_string(G.seqN) + "_" + nw +
+               " (stencil, thread per event) + k_gen_batch (keys handed over)";
     } else if (chn_on(e)) {
         push = "k_chn_batch_" + std::to_string(G.chnN - 1) + "_" + std::to_string(G.chnKW) +
                " (chained states, register window, lane per key) + " +
@@ -2406,7 +2548,8 @@ void gen_flush_deep(GenEngine* e, bool rec) {
     if (e->rec && rec) {   // the register-window kernels' records
         GenArgs a = e->args();
         const GenArgs& ap = a;
-        hipLaunchKernelGGL(e->host.cntOk ? kCntFlush[e->host.absNW] : kAbsFlush[e->host.absNW], dim3((e->K + 63) / 64),
+        hipLaunchKernelGGL(e->host.seqOk ? kSeqFlush[e->host.absNW]
+                           : e->host.cntOk ? kCntFlush[e->host.absNW] : kAbsFlush[e->host.absNW], dim3((e->K + 63) / 64),
                            dim3(64), 0, e->stream, ap);
         GH_OK(hipGetLastError());
     }
