@@ -205,11 +205,14 @@ struct GenProgram {
     uint32_t chnKeepW[2], chnKeepA[2];
     int32_t chnAttrK[GEN_MAXA];
     int32_t chnSlotEv[GEN_MAXSLOT];
-    // the stream-state sequence `every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]` (SEQUENCE, partitioned, one
+    // the stream-state sequence `every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]` (SEQUENCE, one
     // stream, 2 <= n <= 4), which runs on the stencil kernel of seq_kernels.hip (gen_host.hip seq_shape): seqP[i] the
     // processor of state i, seqSlotEv[s] the state whose event slot s holds; filter i as seqNT[i] AND-ed terms, each
-    // a program at most two entries deep (code[seqTpc, +seqTlen)) with its decoded compare (seqFF.on) when it is one
-    int32_t seqOk, seqN;
+    // a program at most two entries deep (code[seqTpc, +seqTlen)) with its decoded compare (seqFF.on) when it is one.
+    // seqFlat: the query is unpartitioned (one key, the batch in arrival order: the flat kernel); seqProj: the select
+    // list set by sg_set_projection is one the batch kernels evaluate from the match's window (no aggregators, every
+    // item at most two entries deep)
+    int32_t seqOk, seqN, seqFlat, seqProj;
     int32_t seqP[4];
     int32_t seqSlotEv[GEN_MAXSLOT];
     int32_t seqNT[4];
@@ -282,7 +285,8 @@ struct GenBatch {
     const uint32_t* tpay;
     uint32_t* tileMax;
     // seq_kernels.hip: per element of the key-sorted batch its key, which carry record the batch reads and its rank
-    // in the key's run (k_seq_keys writes it; SEQ_NOKEY: the general kernel walks the key)
+    // in the key's run (k_seq_keys writes it; SEQ_NOKEY: the general kernel walks the key).  The unpartitioned
+    // sequence has no tags: ekey[0] is the carry record the batch reads, or SEQ_NOKEY (k_seq_head writes it)
     uint32_t* ekey;
 };
 

@@ -80,14 +80,18 @@ static const AbsKernel kChnWide[CHN_MAXN - 1][3] = {{k_chn_wide_1_0, k_chn_wide_
                                                     {k_chn_wide_2_0, k_chn_wide_2_1, k_chn_wide_2_2},
                                                     {k_chn_wide_3_0, k_chn_wide_3_1, k_chn_wide_3_2}};
 // [n - 2][attribute words]: the sequence stencil kernels (seq_kernels.hip), their per-key kernels by attribute words
-#define SEQ_DECL(NW) extern "C" __global__ void k_seq_batch_2_##NW(const GenArgs ap); \
-    extern "C" __global__ void k_seq_batch_3_##NW(const GenArgs ap); extern "C" __global__ void k_seq_batch_4_##NW(const GenArgs ap); \
-    extern "C" __global__ void k_seq_keys_##NW(const GenArgs ap); extern "C" __global__ void k_seq_flush_##NW(const GenArgs ap);
+#define SEQ_DECL_V(V, NW) extern "C" __global__ void k_seq_##V##_2_##NW(const GenArgs ap); \
+    extern "C" __global__ void k_seq_##V##_3_##NW(const GenArgs ap); extern "C" __global__ void k_seq_##V##_4_##NW(const GenArgs ap);
+#define SEQ_DECL(NW) SEQ_DECL_V(batch, NW) SEQ_DECL_V(batch, NW##_p) SEQ_DECL_V(flat, NW) SEQ_DECL_V(flat, NW##_p) \
+    extern "C" __global__ void k_seq_keys_##NW(const GenArgs ap); extern "C" __global__ void k_seq_head_##NW(const GenArgs ap); \
+    extern "C" __global__ void k_seq_flush_##NW(const GenArgs ap);
 SEQ_DECL(1) SEQ_DECL(2) SEQ_DECL(3) SEQ_DECL(4)
-static const AbsKernel kSeqBatch[3][CHN_MAXNW + 1] = {{nullptr, k_seq_batch_2_1, k_seq_batch_2_2, k_seq_batch_2_3, k_seq_batch_2_4},
-                                                      {nullptr, k_seq_batch_3_1, k_seq_batch_3_2, k_seq_batch_3_3, k_seq_batch_3_4},
-                                                      {nullptr, k_seq_batch_4_1, k_seq_batch_4_2, k_seq_batch_4_3, k_seq_batch_4_4}};
+// [variant: batch, batch projecting, flat, flat projecting][states - 2][attribute words]
+#define SEQ_ROW(V, N, P) {nullptr, k_seq_##V##_##N##_1##P, k_seq_##V##_##N##_2##P, k_seq_##V##_##N##_3##P, k_seq_##V##_##N##_4##P}
+#define SEQ_TAB(V, P) {SEQ_ROW(V, 2, P), SEQ_ROW(V, 3, P), SEQ_ROW(V, 4, P)}
+static const AbsKernel kSeqBatch[4][3][CHN_MAXNW + 1] = {SEQ_TAB(batch, ), SEQ_TAB(batch, _p), SEQ_TAB(flat, ), SEQ_TAB(flat, _p)};
 static const AbsKernel kSeqKeys[CHN_MAXNW + 1] = {nullptr, k_seq_keys_1, k_seq_keys_2, k_seq_keys_3, k_seq_keys_4};
+static const AbsKernel kSeqHead[CHN_MAXNW + 1] = {nullptr, k_seq_head_1, k_seq_head_2, k_seq_head_3, k_seq_head_4};
 static const AbsKernel kSeqFlush[CHN_MAXNW + 1] = {nullptr, k_seq_flush_1, k_seq_flush_2, k_seq_flush_3, k_seq_flush_4};
 #define ABSF_DECL(NW) extern "C" __global__ void k_abs_flush_##NW(const GenArgs ap);
 ABSF_DECL(1) ABSF_DECL(2) ABSF_DECL(3) ABSF_DECL(4) ABSF_DECL(5) ABSF_DECL(6) ABSF_DECL(7) ABSF_DECL(8)
@@ -625,15 +629,16 @@ static bool seq_terms(const GenProgram& G, uint32_t pc, uint32_t n, std::vector<
 }
 
 // the stream-state sequence shape of seq_kernels.hip:
-//     every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]      (SEQUENCE, partitioned, one stream, 2 <= n <= 4)
+//     every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]      (SEQUENCE, one stream, 2 <= n <= 4)
 // with the processors wired as StateInputStreamParser wires that query (chn_shape's checks: each state's post
 // processor feeding the next state's addState, the last one's reaching the selector, `every` around e1 only, no
 // timers, single-event slots, `within` keyed on e1).  The whole event travels in the payload, so the filters may read
 // any attribute of any earlier state.  Anything else stays on the general kernels, the sequence without `every` too.
+// Unpartitioned, the query is one key whose run is the batch as it arrives: the flat variant (seqFlat).
 void seq_shape(GenProgram& G) {
-    G.seqOk = 0;
+    G.seqOk = G.seqFlat = G.seqProj = 0;
     const int n = G.nprocs;
-    if (G.qtype != SG_Q_SEQUENCE || !G.partitioned || G.nstreams != 1 || n < 2 || n > 4 || G.nslots != n ||
+    if (G.qtype != SG_Q_SEQUENCE || G.nstreams != 1 || n < 2 || n > 4 || G.nslots != n ||
         G.nStartup != 0 || G.MC != 1 || G.nAll != n || G.nReset != n || G.nUpdate != n)
         return;
     const GenRecv& R = G.recv[0];
@@ -679,6 +684,7 @@ void seq_shape(GenProgram& G) {
         }
     }
     G.seqN = n;
+    G.seqFlat = G.partitioned ? 0 : 1;
     G.seqOk = getenv("SG_NO_SEQ") ? 0 : 1;  // (SG_NO_SEQ: A/B timing against the general kernels; same results)
 }
 
@@ -1643,9 +1649,10 @@ GenEngine* gen_create(const uint32_t* ir, size_t nw, const sg_config& cfg, hipSt
                     e->deep = e->dalloc<uint32_t>((size_t)dl.words * K);
                 }
             }
-            // (the sequence kernel: its pair of carry records per key, and a tag per batch element)
+            // (the sequence kernel: its pair of carry records per key, and a tag per batch element; the flat variant
+            // has one key and, instead of the tags, the word its head kernel publishes)
             const uint64_t rw = G.seqOk ? 2ull * seq_rec_rows(G.absNW, (uint32_t)G.seqN) : gen_rec_words(G.absNW, G.cntOk ? 0u : G.Q);
-            if (G.seqOk) e->ekey = e->dalloc<uint32_t>(B);
+            if (G.seqOk) e->ekey = e->dalloc<uint32_t>(G.seqFlat ? 1 : B);
             const bool regKernels = G.cntOk || G.seqOk || (G.playback && G.partitioned && G.nStartup == 1 && e->keyorder);
             if (regKernels && !getenv("SG_NO_REC") && rw * 4 * K <= (64ull << 30)) {
                 // the register-window kernels' records (GEN_W0_REG): a key's window coalesced across the wave's
@@ -1708,7 +1715,7 @@ static size_t type_size(int t) {
 
 // the kernels take GenArgs (616 B) by value in their kernel arguments
 enum { GEN_L_BATCH = 0, GEN_L_TIMERS = 1, GEN_L_DEADLINES = 2, GEN_L_ABS_BATCH = 3, GEN_L_ABS_TIMERS = 4, GEN_L_CNT_BATCH = 5,
-       GEN_L_ABSD_BATCH = 6, GEN_L_ABSD_TIMERS = 7, GEN_L_CHN_BATCH = 8, GEN_L_CHN_WIDE = 9, GEN_L_SEQ_BATCH = 10 };
+       GEN_L_ABSD_BATCH = 6, GEN_L_ABSD_TIMERS = 7, GEN_L_CHN_BATCH = 8, GEN_L_CHN_WIDE = 9, GEN_L_SEQ_BATCH = 10, GEN_L_SEQ_FLAT = 11 };
 // the general kernels over the keys a register-window kernel handed over: a fixed grid striding the list
 #define GEN_FB_BLOCKS 1024u
 // timer sweeps: a fixed grid of one-wave blocks striding over the due keys (their number is on the device)
@@ -1740,11 +1747,13 @@ static bool absd_on(const GenEngine* e) { return e->fb2_list && absd_lds(e) <= 6
 static bool cnt_on(const GenEngine* e) { return e->host.cntOk && e->host.projN == 0 && e->fb_list; }
 // the chain kernel of chn_kernels.hip runs this query (the shape, no device projection)
 static bool chn_on(const GenEngine* e) { return e->host.chnOk && e->host.projN == 0 && e->fb_list; }
-// the stencil kernel of seq_kernels.hip runs this query (the shape, no device projection, its records; key ids fit
-// the element tags)
-static bool seq_on(const GenEngine* e) {
-    return e->host.seqOk && e->host.projN == 0 && e->fb_list && e->rec && e->ekey && e->K < SEQ_KEYMASK;
+// the stencil kernels of seq_kernels.hip run this query (the shape, no device projection or one they evaluate from the
+// match's window, their records): the partitioned one (key ids fit the element tags) or the flat one
+static bool seq_any(const GenEngine* e) {
+    return e->host.seqOk && (e->host.projN == 0 || e->host.seqProj) && e->fb_list && e->rec && e->ekey;
 }
+static bool seq_on(const GenEngine* e) { return seq_any(e) && !e->host.seqFlat && e->K < SEQ_KEYMASK; }
+static bool seq_flat_on(const GenEngine* e) { return seq_any(e) && e->host.seqFlat && e->K == 1; }
 static bool chn_wide_on(const GenEngine* e) { return chn_on(e) && e->host.chnWide && e->fb2_list; }
 // the kernels that read the key-sorted payload with every attribute word of the event
 static bool pay_on(const GenEngine* e) { return abs_on(e) || cnt_on(e) || chn_on(e) || seq_on(e); }
@@ -1784,7 +1793,16 @@ static void launch_gen(GenEngine* e, GenArgs a, int which) {
         // workgroup, then the workgroups' counter rows
         const uint32_t NW = e->host.absNW, T = 256u - ((uint32_t)e->host.seqN - 1u), wg = (a.b.n + T - 1u) / T;
         hipLaunchKernelGGL(kSeqKeys[NW], dim3(blocks), dim3(64), 0, e->stream, ap);
-        hipLaunchKernelGGL(kSeqBatch[e->host.seqN - 2][NW], dim3(wg), dim3(256), 0, e->stream, ap);
+        hipLaunchKernelGGL(kSeqBatch[e->host.projN ? 1 : 0][e->host.seqN - 2][NW], dim3(wg), dim3(256), 0, e->stream, ap);
+        hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((wg + 1023) / 1024, 16u)), dim3(256), 0,
+                           e->stream, e->wstats, wg, e->stats);
+    }
+    else if (which == GEN_L_SEQ_FLAT) {
+        // one wave for key 0 (adopt / hand over, the record to read), one thread per event of the batch as it arrived
+        // (its count in the arguments) with an n - 1 halo per workgroup, then the workgroups' counter rows
+        const uint32_t NW = e->host.absNW, T = 256u - ((uint32_t)e->host.seqN - 1u), wg = (a.b.n + T - 1u) / T;
+        hipLaunchKernelGGL(kSeqHead[NW], dim3(1), dim3(64), 0, e->stream, ap);
+        hipLaunchKernelGGL(kSeqBatch[e->host.projN ? 3 : 2][e->host.seqN - 2][NW], dim3(wg), dim3(256), 0, e->stream, ap);
         hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((wg + 1023) / 1024, 16u)), dim3(256), 0,
                            e->stream, e->wstats, wg, e->stats);
     }
@@ -1865,7 +1883,7 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
         cl.add(e->seg_end, (size_t)e->K * 4);
         cl.add(e->raw_count, 8 * GEN_RAWSEG);
         cl.add(e->t_multi, 4);
-        if (pay_on(e)) cl.add(e->fb_n, 8);
+        if (pay_on(e) || seq_flat_on(e)) cl.add(e->fb_n, 8);
         if ((abs_on(e) && absd_on(e)) || chn_wide_on(e)) cl.add(e->fb2_n, 8);
         GH_OK(cl.launch(e->stream));
     }
@@ -2024,6 +2042,15 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
         a.b.ekey = e->ekey;
         a.mode = GEN_M_TFIRST;   // (this shape emits at most one match per event)
         launch_gen(e, a, GEN_L_SEQ_BATCH);
+        a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
+    } else if (seq_flat_on(e)) {
+        // the flat stencil kernel over the batch as it arrived; the general kernel when key 0's state was not adopted
+        a.fb_list = e->fb_list;
+        a.fb_n = e->fb_n;
+        a.fb_start = e->fb_start;
+        a.b.ekey = e->ekey;
+        a.mode = GEN_M_TFIRST;
+        launch_gen(e, a, GEN_L_SEQ_FLAT);
         a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
     } else if (chn_on(e)) {
         // the chain kernel, then the general kernel over the keys it handed over (from the event where each stopped)
@@ -2369,6 +2396,17 @@ int gen_set_projection(GenEngine* e, const uint32_t* code, uint32_t words, const
     G.ncode += words;
     G.projN = n;
     G.projAgg = A;
+    // the sequence kernels project from the match's window: no aggregators, every item at most two entries deep and
+    // without ifThenElse (jo_eval<false>, as seq_terms asks of the filters), reading the stream's own attributes
+    G.seqProj = G.seqOk && A == 0;
+    for (uint32_t i = 0; i < n && G.seqProj; i++) {
+        const int d = prog_depth(G.code, G.projPc[i], G.projLen[i]);
+        if (d < 0 || d > 2) G.seqProj = 0;
+        for (uint32_t w = G.projPc[i]; w < G.projPc[i] + G.projLen[i]; w += (uint32_t)sg_op_len(G.code[w] & 0xffu))
+            if ((G.code[w] & 0xffu) == SG_OP_VAR && ((G.code[w] >> 16) & 0xffu) != SG_PROJ_SLOT_OUT &&
+                G.code[w + 1] >= (uint32_t)G.nattr[0])
+                G.seqProj = 0;
+    }
     G.projOff = e->recWords;
     e->recWords += 3 * (S + H);
     if (A) {  // the aggregators' per-key state joins the key blocks (no push yet: all zero)
@@ -2484,8 +2522,13 @@ std::string gen_describe(const GenEngine* e) {
     } else if (cnt_on(e)) {
         push = "k_cnt_batch_" + nw + " (register window, lane per key) + k_gen_batch (keys handed over)";
     } else if (seq_on(e)) {
-        push = "k_seq_keys_" + nw + " (lane per key) + k_seq_batch_" + std::to_string(G.seqN) + "_" + nw +
-               " (stencil, thread per event) + k_gen_batch (keys handed over)";
+        push = "k_seq_keys_" + nw + " (lane per key) + k_seq_batch_" + std::to_string(G.seqN) + "_" + nw + (G.projN ? "_p" : "") +
+               (G.projN ? " (stencil, thread per event, select list projected)" : " (stencil, thread per event)") +
+               " + k_gen_batch (keys handed over)";
+    } else if (seq_flat_on(e)) {
+        push = "k_seq_head_" + nw + " (one wave) + k_seq_flat_" + std::to_string(G.seqN) + "_" + nw + (G.projN ? "_p" : "") +
+               (G.projN ? " (flat stencil, thread per event, select list projected)" : " (flat stencil, thread per event)") +
+               " + k_gen_batch (key 0 handed over)";
     } else if (chn_on(e)) {
         push = "k_chn_batch_" + std::to_string(G.chnN - 1) + "_" + std::to_string(G.chnKW) +
                " (chained states, register window, lane per key) + " +

@@ -1,6 +1,6 @@
-// seq_kernels.hip — stencil kernel for partitioned sequences of stream states
+// seq_kernels.hip — stencil kernels for sequences of stream states, partitioned or not
 //
-//     every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]          (SEQUENCE, partitioned, one stream, 2 <= n <= 4)
+//     every e1=S[f0], e2=S[f1], ..., en=S[f(n-1)] [within W]          (SEQUENCE, one stream, 2 <= n <= 4)
 //
 // The general kernel (gen_kernels.hip) runs this query through the processor graph, one lane per key.  Under
 // SEQUENCE semantics the graph does very little per event (paths under
@@ -36,6 +36,17 @@
 // The carry of a key is a pair of records: the thread of a run's last event writes the record the batch does NOT
 // read (GEN_W0_SEQP, flipped by k_seq_keys before the batch kernel), so threads of the same run in other workgroups
 // that still read the old carry never race with it, and untouched keys cost nothing.
+//
+// The unpartitioned query is one key whose run is the whole batch in arrival order, so it needs no grouping, no
+// payload and no tags:
+//   k_seq_head_<NW>      one wave, before the batch kernel: what k_seq_keys does for key 0 (adopt or hand over, flip
+//                        GEN_W0_SEQP), and the record to read published in one device word (GenBatch.ekey[0])
+//   k_seq_flat_<n>_<NW>  the same tile, phases and emission over the columns themselves: a thread's element is its
+//                        global index, its rank that index clipped to n - 1, the element count a launch argument; the
+//                        thread of the batch's last event writes the other record
+// With a select list set (gen_host.hip gen_set_projection: no aggregators, every item at most two entries deep) the
+// `_p` instantiations of both batch kernels evaluate the items from the emitting thread's window and write them to
+// the raw record where the general kernel's projectSelect puts them.
 #include <hip/hip_runtime.h>
 
 #include "../../include/siddhi_gpu.h"
@@ -154,6 +165,26 @@ template <int NW> __device__ bool seq_adopt(const GenArgs& a, uint32_t key) {
     return true;
 }
 
+// the record a batch reads of a key it touches, the key's other record made current (GEN_W0_SEQP flipped); a key whose
+// state arrives in its block is adopted first.  false: the general kernel walks the key's run
+template <int NW> __device__ __forceinline__ bool seq_claim(const GenArgs& a, const cGenProgram& G, uint32_t key, uint32_t& rd) {
+    gu32& w0r = gp(a.state)[gen_il(a.K, key, 0)];
+    const uint32_t w0 = w0r;
+    rd = 0;
+    if (w0 & GEN_W0_REG) {
+        rd = (w0 & GEN_W0_SEQP) ? 1u : 0u;
+        w0r = w0 ^ GEN_W0_SEQP;
+    } else if (!(w0 & 1u)) {   // PartitionRuntimeImpl.initPartition: the seed state 0 stages dies at the first event
+        SeqRec<NW>(a, (uint32_t)G.seqN, key).at(0u, 0u) = 0u;
+        w0r = 1u | GEN_W0_REG | GEN_W0_SEQP;
+    } else if (seq_adopt<NW>(a, key)) {
+        w0r = 1u | GEN_W0_REG | GEN_W0_SEQP;
+    } else {
+        return false;
+    }
+    return true;
+}
+
 // ---- keys: one lane per key, before the batch kernel ----
 template <int NW> __device__ void seq_keys(const GenArgs& a) {
     const uint32_t key = blockIdx.x * 64u + threadIdx.x, lane = threadIdx.x & 63u;
@@ -166,20 +197,8 @@ template <int NW> __device__ void seq_keys(const GenArgs& a) {
     bool fb = false;
     uint32_t tag = SEQ_NOKEY;
     if (b < e) {
-        gu32& w0r = gp(a.state)[gen_il(a.K, key, 0)];
-        const uint32_t w0 = w0r;
-        uint32_t rd = 0;
-        if (w0 & GEN_W0_REG) {
-            rd = (w0 & GEN_W0_SEQP) ? 1u : 0u;
-            w0r = w0 ^ GEN_W0_SEQP;
-        } else if (!(w0 & 1u)) {   // PartitionRuntimeImpl.initPartition: the seed state 0 stages dies at the first event
-            SeqRec<NW>(a, (uint32_t)G.seqN, key).at(0u, 0u) = 0u;
-            w0r = 1u | GEN_W0_REG | GEN_W0_SEQP;
-        } else if (seq_adopt<NW>(a, key)) {
-            w0r = 1u | GEN_W0_REG | GEN_W0_SEQP;
-        } else {
-            fb = true;
-        }
+        uint32_t rd;
+        fb = !seq_claim<NW>(a, G, key, rd);
         if (!fb) tag = key | (rd << 29);
     }
     gu32* ek = gp(a.b.ekey);
@@ -197,6 +216,20 @@ template <int NW> __device__ void seq_keys(const GenArgs& a) {
     abs_fallback(a, fb, key, b);
     const unsigned long long fm = __ballot(fb);   // (sg_stats.window_spills: keys handed to the general kernel)
     if (fm && lane == 0) atomicAdd(&a.o.stats[GST_SPILLS], (unsigned long long)__popcll(fm));
+}
+
+// ---- head: the unpartitioned query's one key, one wave before the flat kernel ----
+// GenBatch.ekey[0]: the record the batch reads, or SEQ_NOKEY when key 0 went to the hand-over list
+template <int NW> __device__ void seq_head(const GenArgs& a) {
+    const cGenProgram& G = *(cGenProgram*)a.G;
+    bool fb = false;
+    if ((threadIdx.x & 63u) == 0u) {
+        uint32_t rd;
+        fb = !seq_claim<NW>(a, G, 0u, rd);
+        gp(a.b.ekey)[0] = fb ? SEQ_NOKEY : rd;
+        if (fb) atomicAdd(&a.o.stats[GST_SPILLS], 1ull);   // (sg_stats.window_spills)
+    }
+    abs_fallback(a, fb, 0u, 0u);
 }
 
 // ---- batch: one thread per event of the key-sorted batch ----
@@ -243,27 +276,33 @@ template <int NW> __device__ __forceinline__ GVal seq_word(const cGenProgram& G,
 }
 
 // filter M on a partial of M events and this event: win[N - 1] is the event, win[N - 1 - d] the key's event d back
+// slot s of a partial of M events and this event: the state whose event it holds, -1: an empty slot
+template <int M> __device__ __forceinline__ int seq_state_of(const cGenProgram& G, uint32_t s, int32_t c) {
+    const int t = s < (uint32_t)GEN_MAXSLOT ? G.seqSlotEv[s] : -1;
+    return (t < 0 || t > M || !(c == 0 || c == -1)) ? -1 : t;   // (single-event slots: index 0 or `last`)
+}
+// attribute `at` of that slot's event: win[N - 1] is this event, win[N - 1 - d] the key's event d back
+template <int N, int NW, int M> __device__ __forceinline__ GVal seq_var(const cGenProgram& G, const AbsEv<NW> (&win)[N],
+                                                                      uint32_t s, uint32_t at, int32_t c) {
+    const int t = seq_state_of<M>(G, s, c);
+    if (t < 0) return GVal{0, true};
+    uint32_t w[NW], nb = 0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) w[q] = 0;
+#pragma unroll
+    for (int j = N - 1 - M; j < N; ++j) {   // (selects: no indexing of the register window)
+        const bool here = j == N - 1 - M + t;
+#pragma unroll
+        for (int q = 0; q < NW; ++q) w[q] = here ? win[j].w[q] : w[q];
+        nb = here ? win[j].nb : nb;
+    }
+    return seq_word<NW>(G, w, nb, at);
+}
+
 template <int N, int NW, int M> __device__ __forceinline__ bool seq_filter(const cGenProgram& G, const AbsEv<NW> (&win)[N],
                                                                          uint32_t& err) {
-    auto stateOf = [&](uint32_t s, int32_t c) -> int {   // the state whose event slot s holds, -1: an empty slot
-        const int t = s < (uint32_t)GEN_MAXSLOT ? G.seqSlotEv[s] : -1;
-        return (t < 0 || t > M || !(c == 0 || c == -1)) ? -1 : t;   // (single-event slots: index 0 or `last`)
-    };
-    auto var_ = [&](uint32_t s, uint32_t at, int32_t c) -> GVal {
-        const int t = stateOf(s, c);
-        if (t < 0) return GVal{0, true};
-        uint32_t w[NW], nb = 0;
-#pragma unroll
-        for (int q = 0; q < NW; ++q) w[q] = 0;
-#pragma unroll
-        for (int j = N - 1 - M; j < N; ++j) {   // (selects: no indexing of the register window)
-            const bool here = j == N - 1 - M + t;
-#pragma unroll
-            for (int q = 0; q < NW; ++q) w[q] = here ? win[j].w[q] : w[q];
-            nb = here ? win[j].nb : nb;
-        }
-        return seq_word<NW>(G, w, nb, at);
-    };
+    auto stateOf = [&](uint32_t s, int32_t c) -> int { return seq_state_of<M>(G, s, c); };
+    auto var_ = [&](uint32_t s, uint32_t at, int32_t c) -> GVal { return seq_var<N, NW, M>(G, win, s, at, c); };
     const int nt = G.seqNT[M];
     for (int q = 0; q < nt; ++q) {   // (a run-time loop: one copy of the interpreter per filter)
         bool ok;
@@ -277,6 +316,26 @@ template <int N, int NW, int M> __device__ __forceinline__ bool seq_filter(const
         if (!ok) return false;
     }
     return true;
+}
+
+// the select list and `having` of a match from its window, laid out as gen_kernels.hip projectSelect lays them out:
+// 3 words per item (value lo, hi, null) from pv; `having` reads the items just written (SG_PROJ_SLOT_OUT).  No
+// aggregators, every item at most two entries deep (gen_host.hip gen_set_projection checked it)
+template <int N, int NW> __device__ __forceinline__ void seq_project(const cGenProgram& G, const AbsEv<NW> (&win)[N], gu32* pv,
+                                                                     uint32_t& err) {
+    for (uint32_t i = 0; i < G.projN; i++) {   // (a run-time loop: one copy of the interpreter)
+        const GVal v = jo_eval<false>(G.code, G.projPc[i], G.projLen[i], err,
+                                      [&](uint32_t s, uint32_t at, int32_t c) -> GVal {
+                                          if (s == SG_PROJ_SLOT_OUT)
+                                              return GVal{(uint64_t)pv[3 * at] | ((uint64_t)pv[3 * at + 1] << 32),
+                                                          pv[3 * at + 2] != 0};
+                                          return seq_var<N, NW, N - 1>(G, win, s, at, c);
+                                      },
+                                      [&](uint32_t s, int32_t c) -> bool { return seq_state_of<N - 1>(G, s, c) < 0; });
+        pv[3 * i] = (uint32_t)v.b;
+        pv[3 * i + 1] = (uint32_t)(v.b >> 32);
+        pv[3 * i + 2] = v.null ? 1u : 0u;
+    }
 }
 
 struct SeqOut {
@@ -317,14 +376,107 @@ template <int N, int NW> struct SeqPhase {
     }
 };
 
-template <int N, int NW> __device__ __forceinline__ void seq_batch(const GenArgs& a) {
+// ---- the tail both batch kernels share: the match record, the carry record, the counter row ----
+// the match: one raw record, reserved per wave (StreamPostStateProcessor -> QuerySelector input); PROJ: with the
+// select list's items behind it
+template <int N, int NW, bool PROJ>
+__device__ __forceinline__ void seq_emit(const GenArgs& a, const cGenProgram& G, const AbsEv<NW> (&win)[N], bool match,
+                                         uint32_t pos, uint32_t key, uint32_t& err) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long mm = __ballot(match);
+    if (!mm) return;
+    const int leader = __ffsll((long long)mm) - 1;
+    const uint32_t sg = (blockIdx.x * (SEQ_TB / 64u) + wv) % a.o.nseg;
+    unsigned long long base = 0;
+    if ((int)lane == leader) base = atomicAdd(&a.o.raw_count[sg], (unsigned long long)__popcll(mm));
+    base = __shfl(base, leader, 64);
+    if (!match) return;
+    const unsigned long long r = (unsigned long long)sg * a.o.seg_cap + base + __popcll(mm & ((1ull << lane) - 1ull));
+    if (r >= (unsigned long long)(sg + 1) * a.o.seg_cap) {
+        err |= GERR_MATCHCAP;
+        return;
+    }
+    gu32* out = gp(a.o.raw) + r * a.o.recWords;
+    const AbsEv<NW>& ev = win[N - 1];
+    out[0] = pos;
+    out[1] = 0u;
+    out[2] = (uint32_t)ev.seq;
+    out[3] = (uint32_t)(ev.seq >> 32);
+    out[4] = (uint32_t)(uint64_t)ev.ts;
+    out[5] = (uint32_t)((uint64_t)ev.ts >> 32);
+    out[6] = key;
+    gu32* lens = out + 7;
+    gu32* seqs = lens + G.nslots;
+    for (int s = 0; s < G.nslots; s++) {   // (n slots, one event each: slot s at s * MC, MC = 1)
+        const int t = G.seqSlotEv[s];
+        uint64_t q = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) q = j == t ? win[j].seq : q;
+        lens[s] = 1u;
+        seqs[2 * s] = (uint32_t)q;
+        seqs[2 * s + 1] = (uint32_t)(q >> 32);
+    }
+    if constexpr (PROJ) seq_project<N, NW>(G, win, out + G.projOff, err);
+    gp(a.o.t_cnt)[pos] = 1u;
+    if (a.mode & GEN_M_TFIRST) gp(a.o.t_first)[pos] = (uint32_t)r;
+}
+
+// the carry after a run's last event (rank rk, cnt events read from the old record): the newest n - 1 of them
+template <int N, int NW>
+__device__ __forceinline__ void seq_carry(const SeqRec<NW>& rec, uint32_t c, uint32_t rk, uint32_t cnt, uint32_t abits,
+                                          const AbsEv<NW> (&win)[N]) {
+    constexpr uint32_t H = N - 1;
+    const uint32_t have = rk + 1u + cnt;
+    const uint32_t nc = have < H ? have : H;
+    rec.at(c, 0u) = nc | (abits << 4);
+#pragma unroll
+    for (uint32_t j = 0; j < H; ++j)
+        if (j < nc) rec.store(c, j, win[N - 1 - j]);
+}
+
+// the work counters of the general kernel, one row per workgroup (every thread calls this)
+__device__ __forceinline__ void seq_stats(const GenArgs& a, unsigned long long sc, unsigned long long cr, unsigned long long ma,
+                                          unsigned long long ky, uint32_t err, unsigned long long (*sStat)[4]) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    for (int off = 32; off > 0; off >>= 1) {
+        sc += __shfl_xor(sc, off, 64);
+        cr += __shfl_xor(cr, off, 64);
+        ma += __shfl_xor(ma, off, 64);
+        ky += __shfl_xor(ky, off, 64);
+        err |= (uint32_t)__shfl_xor((int)err, off, 64);
+    }
+    if (lane == 0) {
+        if (err) atomicOr(a.o.err, err);
+        sStat[wv][0] = sc;
+        sStat[wv][1] = cr;
+        sStat[wv][2] = ma;
+        sStat[wv][3] = ky;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t w = 0; w < SEQ_TB / 64u; w++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) t[c] += sStat[w][c];
+        auto row = gp(a.o.wstats) + (size_t)blockIdx.x * GST_N;
+        row[GST_SCANNED] = t[0];
+        row[GST_CREATED] = t[1];
+        row[GST_MATCHES] = t[2];
+        row[GST_KEYS] = t[3];
+        row[GST_LIVE0] = 0;
+        row[GST_SPILLS] = 0;
+    }
+}
+
+template <int N, int NW, bool PROJ> __device__ __forceinline__ void seq_batch(const GenArgs& a) {
     constexpr uint32_t H = N - 1, T = SEQ_TB - H;
     __shared__ uint32_t sE[4 + NW][SEQ_TB];   // the decoded events: batch position, ts lo, hi, null bits, words
     __shared__ uint32_t sK[SEQ_TB + 1];       // their tags, and the tag of the element after the tile
     __shared__ uint32_t sA[H][SEQ_TB];        // A_1 .. A_{n-1} of each element
     __shared__ unsigned long long sStat[SEQ_TB / 64][4];
     const cGenProgram& G = *(cGenProgram*)a.G;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t nv = gp(a.b.seg_end)[a.K - 1];   // elements of the key-sorted batch (null keys dropped)
     const int64_t g = (int64_t)blockIdx.x * T + tid - H;
     const bool valid = g >= 0 && g < (int64_t)nv;
@@ -390,91 +542,92 @@ template <int N, int NW> __device__ __forceinline__ void seq_batch(const GenArgs
         }
     }
     const SeqOut o = SeqPhase<N, NW>::template run<0>(G, win, mine, rk == 0u, cbits, sA, SeqOut{0u, mine ? 1u : 0u, 0u, false});
-    const uint32_t abits = o.abits, scanned = o.scanned;
+    const uint32_t abits = o.abits;
     uint32_t err = o.err;
-    bool match = o.match;
     const bool own = mine && tid >= H;   // (the halo threads' elements belong to the workgroup before)
-    match = match && own;
-    // ---- the match: one raw record, reserved per wave (StreamPostStateProcessor -> QuerySelector input) ----
-    const unsigned long long mm = __ballot(match);
-    if (mm) {
-        const int leader = __ffsll((long long)mm) - 1;
-        const uint32_t sg = (blockIdx.x * (SEQ_TB / 64u) + wv) % a.o.nseg;
-        unsigned long long base = 0;
-        if ((int)lane == leader) base = atomicAdd(&a.o.raw_count[sg], (unsigned long long)__popcll(mm));
-        base = __shfl(base, leader, 64);
-        if (match) {
-            const unsigned long long r = (unsigned long long)sg * a.o.seg_cap + base + __popcll(mm & ((1ull << lane) - 1ull));
-            if (r >= (unsigned long long)(sg + 1) * a.o.seg_cap) {
-                err |= GERR_MATCHCAP;
-            } else {
-                gu32* out = gp(a.o.raw) + r * a.o.recWords;
-                const AbsEv<NW>& ev = win[N - 1];
-                out[0] = pos;
-                out[1] = 0u;
-                out[2] = (uint32_t)ev.seq;
-                out[3] = (uint32_t)(ev.seq >> 32);
-                out[4] = (uint32_t)(uint64_t)ev.ts;
-                out[5] = (uint32_t)((uint64_t)ev.ts >> 32);
-                out[6] = key;
-                gu32* lens = out + 7;
-                gu32* seqs = lens + G.nslots;
-                for (int s = 0; s < G.nslots; s++) {   // (n slots, one event each: slot s at s * MC, MC = 1)
-                    const int t = G.seqSlotEv[s];
-                    uint64_t q = 0;
+    const bool match = o.match && own;
+    seq_emit<N, NW, PROJ>(a, G, win, match, pos, key, err);
+    // the carry: the thread of the run's last event writes the record this batch does not read
+    const uint32_t nxt = sK[tid + 1];
+    if (own && !(nxt != SEQ_NOKEY && (nxt & SEQ_KEYMASK) == key)) seq_carry<N, NW>(rec, rd ^ 1u, rk, cnt, abits, win);
+    seq_stats(a, own ? o.scanned : 0u, (own && (abits & 1u)) ? 1u : 0u, match ? 1u : 0u, (own && rk == 0u) ? 1u : 0u, err,
+              sStat);
+}
+
+// ---- flat: one thread per event of the unpartitioned batch, in arrival order ----
+// The batch is key 0's run: element g is batch position g, its rank min(g, n - 1), the events before it the tile's or
+// (the first n - 1 elements of the batch) the carry record k_seq_head published.  Consecutive threads read consecutive
+// positions of ts and of every column.
+template <int N, int NW, bool PROJ> __device__ __forceinline__ void seq_flat(const GenArgs& a) {
+    constexpr uint32_t H = N - 1, T = SEQ_TB - H;
+    __shared__ uint32_t sE[3 + NW][SEQ_TB];   // the decoded events: ts lo, hi, null bits, words
+    __shared__ uint32_t sA[H][SEQ_TB];        // A_1 .. A_{n-1} of each element
+    __shared__ unsigned long long sStat[SEQ_TB / 64][4];
+    const cGenProgram& G = *(cGenProgram*)a.G;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t rd = gp(a.b.ekey)[0];   // (one word, the same for every workgroup)
+    if (rd == SEQ_NOKEY) {   // key 0 is on the hand-over list: the general kernel walks the batch
+        seq_stats(a, 0u, 0u, 0u, 0u, 0u, sStat);
+        return;
+    }
+    const uint32_t n = a.b.n;
+    const int64_t g = (int64_t)blockIdx.x * T + tid - H;
+    const bool mine = g >= 0 && g < (int64_t)n;
+    const uint32_t pos = mine ? (uint32_t)g : 0u, rk = pos < H ? pos : H;
+    AbsEv<NW> win[N];
 #pragma unroll
-                    for (int j = 0; j < N; ++j) q = j == t ? win[j].seq : q;
-                    lens[s] = 1u;
-                    seqs[2 * s] = (uint32_t)q;
-                    seqs[2 * s + 1] = (uint32_t)(q >> 32);
-                }
-                gp(a.o.t_cnt)[pos] = 1u;
-                if (a.mode & GEN_M_TFIRST) gp(a.o.t_first)[pos] = (uint32_t)r;
+    for (int j = 0; j < N; ++j) {
+        win[j].ts = 0;
+        win[j].seq = 0;
+        win[j].nb = 0;
+#pragma unroll
+        for (int q = 0; q < NW; ++q) win[j].w[q] = 0;
+    }
+    if (mine) {
+        win[N - 1].ts = gp(a.b.ts)[pos];
+        win[N - 1].seq = a.b.seq_base + pos;
+        seq_gather<NW>(a, G, pos, win[N - 1]);
+    }
+    sE[0][tid] = (uint32_t)(uint64_t)win[N - 1].ts;
+    sE[1][tid] = (uint32_t)((uint64_t)win[N - 1].ts >> 32);
+    sE[2][tid] = win[N - 1].nb;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) sE[3 + q][tid] = win[N - 1].w[q];
+    __syncthreads();
+    // the window: the event d back from the tile, else (the batch's first n - 1 elements) from the carry record;
+    // what the halo threads cannot reach is never used
+    const SeqRec<NW> rec(a, (uint32_t)N, 0u);
+    uint32_t cnt = 0, cbits = 0;
+    if (mine && rk < H) {
+        const uint32_t h = rec.at(rd, 0u);
+        cnt = h & 15u;
+        cbits = (h >> 4) & 7u;
+    }
+#pragma unroll
+    for (uint32_t d = 1; d <= H; ++d) {
+        AbsEv<NW>& w = win[N - 1 - d];
+        if (mine && rk >= d) {
+            if (tid >= d) {
+                const uint32_t s = tid - d;
+                w.seq = a.b.seq_base + (pos - d);
+                w.ts = (int64_t)((uint64_t)sE[0][s] | ((uint64_t)sE[1][s] << 32));
+                w.nb = sE[2][s];
+#pragma unroll
+                for (int q = 0; q < NW; ++q) w.w[q] = sE[3 + q][s];
             }
+        } else if (mine && d - rk - 1u < cnt) {
+            rec.load(rd, d - rk - 1u, w);
         }
     }
-    // ---- the carry: the thread of the run's last event writes the record this batch does not read ----
-    const uint32_t nxt = sK[tid + 1];
-    if (own && !(nxt != SEQ_NOKEY && (nxt & SEQ_KEYMASK) == key)) {
-        const uint32_t have = rk + 1u + cnt;
-        const uint32_t nc = have < H ? have : H;
-        rec.at(rd ^ 1u, 0u) = nc | (abits << 4);
-#pragma unroll
-        for (uint32_t j = 0; j < H; ++j)
-            if (j < nc) rec.store(rd ^ 1u, j, win[N - 1 - j]);
-    }
-    // ---- the work counters of the general kernel, per workgroup ----
-    unsigned long long sc = own ? scanned : 0u, cr = (own && (abits & 1u)) ? 1u : 0u, ma = match ? 1u : 0u,
-                       ky = (own && rk == 0u) ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) {
-        sc += __shfl_xor(sc, off, 64);
-        cr += __shfl_xor(cr, off, 64);
-        ma += __shfl_xor(ma, off, 64);
-        ky += __shfl_xor(ky, off, 64);
-        err |= (uint32_t)__shfl_xor((int)err, off, 64);
-    }
-    if (lane == 0) {
-        if (err) atomicOr(a.o.err, err);
-        sStat[wv][0] = sc;
-        sStat[wv][1] = cr;
-        sStat[wv][2] = ma;
-        sStat[wv][3] = ky;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (uint32_t w = 0; w < SEQ_TB / 64u; w++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) t[c] += sStat[w][c];
-        auto row = gp(a.o.wstats) + (size_t)blockIdx.x * GST_N;
-        row[GST_SCANNED] = t[0];
-        row[GST_CREATED] = t[1];
-        row[GST_MATCHES] = t[2];
-        row[GST_KEYS] = t[3];
-        row[GST_LIVE0] = 0;
-        row[GST_SPILLS] = 0;
-    }
+    const SeqOut o = SeqPhase<N, NW>::template run<0>(G, win, mine, rk == 0u, cbits, sA, SeqOut{0u, mine ? 1u : 0u, 0u, false});
+    const uint32_t abits = o.abits;
+    uint32_t err = o.err;
+    const bool own = mine && tid >= H;
+    const bool match = o.match && own;
+    seq_emit<N, NW, PROJ>(a, G, win, match, pos, 0u, err);
+    if (own && pos == n - 1u) seq_carry<N, NW>(rec, rd ^ 1u, rk, cnt, abits, win);   // the batch's last event
+    seq_stats(a, own ? o.scanned : 0u, (own && (abits & 1u)) ? 1u : 0u, match ? 1u : 0u, (own && pos == 0u) ? 1u : 0u, err,
+              sStat);
 }
 
 // ---- the records written back to the blocks (before a snapshot, a state export, the min-seq scan, a purge) ----
@@ -550,16 +703,28 @@ template <int NW> __device__ void seq_flush(const GenArgs& a) {
 
 }  // namespace
 
-// One batch kernel per (states, attribute words of the event); the per-key kernels per word count.  The batch kernel
-// reads its GenArgs through the kernarg segment (gen_kernels.hip gen_kernarg: the column arrays are indexed at run
-// time, and the by-value parameter would be copied into every lane's scratch for that).
+// One batch kernel per (states, attribute words of the event) and variant (partitioned / flat, bare / projecting: the
+// projecting code is in instantiations of its own, so a launch without a select list pays nothing for it); the
+// per-key kernels per word count.  The batch kernels read their GenArgs through the kernarg segment (gen_kernels.hip
+// gen_kernarg: the column arrays are indexed at run time, and the by-value parameter would be copied into every
+// lane's scratch for that).
 #define SEQ_BATCH(N, NW)                                                                                    \
     extern "C" __global__ void __launch_bounds__(256) k_seq_batch_##N##_##NW(const GenArgs ap) {           \
-        seq_batch<N, NW>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());             \
+        seq_batch<N, NW, false>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());      \
+    }                                                                                                       \
+    extern "C" __global__ void __launch_bounds__(256) k_seq_batch_##N##_##NW##_p(const GenArgs ap) {          \
+        seq_batch<N, NW, true>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());       \
+    }                                                                                                       \
+    extern "C" __global__ void __launch_bounds__(256) k_seq_flat_##N##_##NW(const GenArgs ap) {            \
+        seq_flat<N, NW, false>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());       \
+    }                                                                                                       \
+    extern "C" __global__ void __launch_bounds__(256) k_seq_flat_##N##_##NW##_p(const GenArgs ap) {           \
+        seq_flat<N, NW, true>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());        \
     }
 #define SEQ_KERNELS(NW)                                                                                     \
     SEQ_BATCH(2, NW) SEQ_BATCH(3, NW) SEQ_BATCH(4, NW)                                                      \
     extern "C" __global__ void __launch_bounds__(64) k_seq_keys_##NW(const GenArgs ap) { seq_keys<NW>(ap); } \
+    extern "C" __global__ void __launch_bounds__(64) k_seq_head_##NW(const GenArgs ap) { seq_head<NW>(ap); } \
     extern "C" __global__ void __launch_bounds__(64) k_seq_flush_##NW(const GenArgs ap) { seq_flush<NW>(ap); }
 SEQ_KERNELS(1)
 SEQ_KERNELS(2)
