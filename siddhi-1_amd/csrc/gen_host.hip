@@ -29,87 +29,46 @@
 #include "pinned.h"
 #include "state_doc.h"
 
-extern "C" __global__ void k_gen_batch(const GenArgs ap);
-#define ABS_DECL(NW) extern "C" __global__ void k_abs_batch_##NW(const GenArgs ap); \
-                     extern "C" __global__ void k_abs_batchf_##NW(const GenArgs ap); \
-                     extern "C" __global__ void k_abs_timers_##NW(const GenArgs ap);
-ABS_DECL(1) ABS_DECL(2) ABS_DECL(3) ABS_DECL(4) ABS_DECL(5) ABS_DECL(6) ABS_DECL(7) ABS_DECL(8)
-typedef void (*AbsKernel)(const GenArgs);
-static const AbsKernel kAbsBatch[ABS_MAXNW + 1] = {nullptr, k_abs_batch_1, k_abs_batch_2, k_abs_batch_3, k_abs_batch_4,
-                                                   k_abs_batch_5, k_abs_batch_6, k_abs_batch_7, k_abs_batch_8};
-static const AbsKernel kAbsBatchF[ABS_MAXNW + 1] = {nullptr, k_abs_batchf_1, k_abs_batchf_2, k_abs_batchf_3,
-                                                    k_abs_batchf_4, k_abs_batchf_5, k_abs_batchf_6, k_abs_batchf_7,
-                                                    k_abs_batchf_8};
-#define ABSD_DECL(NW) extern "C" __global__ void k_absd_batch_##NW(const GenArgs ap); \
-                      extern "C" __global__ void k_absd_timers_##NW(const GenArgs ap); \
-                      extern "C" __global__ void k_absd_batchf_##NW(const GenArgs ap); \
-                      extern "C" __global__ void k_absd_timersf_##NW(const GenArgs ap); \
-                      extern "C" __global__ void k_absd_flush_##NW(const GenArgs ap);
-ABSD_DECL(1) ABSD_DECL(2) ABSD_DECL(3) ABSD_DECL(4) ABSD_DECL(5) ABSD_DECL(6) ABSD_DECL(7) ABSD_DECL(8)
-static const AbsKernel kAbsdBatch[ABS_MAXNW + 1] = {nullptr, k_absd_batch_1, k_absd_batch_2, k_absd_batch_3,
-                                                    k_absd_batch_4, k_absd_batch_5, k_absd_batch_6, k_absd_batch_7,
-                                                    k_absd_batch_8};
-static const AbsKernel kAbsdTimers[ABS_MAXNW + 1] = {nullptr, k_absd_timers_1, k_absd_timers_2, k_absd_timers_3,
-                                                     k_absd_timers_4, k_absd_timers_5, k_absd_timers_6, k_absd_timers_7,
-                                                     k_absd_timers_8};
-static const AbsKernel kAbsdBatchF[ABS_MAXNW + 1] = {nullptr, k_absd_batchf_1, k_absd_batchf_2, k_absd_batchf_3,
-                                                     k_absd_batchf_4, k_absd_batchf_5, k_absd_batchf_6, k_absd_batchf_7,
-                                                     k_absd_batchf_8};
-static const AbsKernel kAbsdTimersF[ABS_MAXNW + 1] = {nullptr, k_absd_timersf_1, k_absd_timersf_2, k_absd_timersf_3,
-                                                      k_absd_timersf_4, k_absd_timersf_5, k_absd_timersf_6,
-                                                      k_absd_timersf_7, k_absd_timersf_8};
-static const AbsKernel kAbsdFlush[ABS_MAXNW + 1] = {nullptr, k_absd_flush_1, k_absd_flush_2, k_absd_flush_3,
-                                                    k_absd_flush_4, k_absd_flush_5, k_absd_flush_6, k_absd_flush_7,
-                                                    k_absd_flush_8};
-#define CNT_DECL(NW) extern "C" __global__ void k_cnt_batch_##NW(const GenArgs ap); \
-    extern "C" __global__ void k_cnt_flush_##NW(const GenArgs ap);
-CNT_DECL(1) CNT_DECL(2) CNT_DECL(3) CNT_DECL(4) CNT_DECL(5) CNT_DECL(6) CNT_DECL(7) CNT_DECL(8)
-static const AbsKernel kCntBatch[ABS_MAXNW + 1] = {nullptr, k_cnt_batch_1, k_cnt_batch_2, k_cnt_batch_3, k_cnt_batch_4,
-                                                   k_cnt_batch_5, k_cnt_batch_6, k_cnt_batch_7, k_cnt_batch_8};
-#define CHN_DECL(NE) extern "C" __global__ void k_chn_batch_##NE##_0(const GenArgs ap); \
-    extern "C" __global__ void k_chn_batch_##NE##_1(const GenArgs ap); extern "C" __global__ void k_chn_batch_##NE##_2(const GenArgs ap);
-CHN_DECL(1) CHN_DECL(2) CHN_DECL(3)
-#define CHNW_DECL(NE) extern "C" __global__ void k_chn_wide_##NE##_0(const GenArgs ap); \
-    extern "C" __global__ void k_chn_wide_##NE##_1(const GenArgs ap); extern "C" __global__ void k_chn_wide_##NE##_2(const GenArgs ap);
-CHNW_DECL(1) CHNW_DECL(2) CHNW_DECL(3)
-// [n - 2][kept words]: the chain kernels (chn_kernels.hip), and their wide-window kernels over the keys handed over
-static const AbsKernel kChnBatch[CHN_MAXN - 1][3] = {{k_chn_batch_1_0, k_chn_batch_1_1, k_chn_batch_1_2},
-                                                     {k_chn_batch_2_0, k_chn_batch_2_1, k_chn_batch_2_2},
-                                                     {k_chn_batch_3_0, k_chn_batch_3_1, k_chn_batch_3_2}};
-static const AbsKernel kChnWide[CHN_MAXN - 1][3] = {{k_chn_wide_1_0, k_chn_wide_1_1, k_chn_wide_1_2},
-                                                    {k_chn_wide_2_0, k_chn_wide_2_1, k_chn_wide_2_2},
-                                                    {k_chn_wide_3_0, k_chn_wide_3_1, k_chn_wide_3_2}};
-// [n - 2][attribute words]: the sequence stencil kernels (seq_kernels.hip), their per-key kernels by attribute words
-#define SEQ_DECL_V(V, NW) extern "C" __global__ void k_seq_##V##_2_##NW(const GenArgs ap); \
-    extern "C" __global__ void k_seq_##V##_3_##NW(const GenArgs ap); extern "C" __global__ void k_seq_##V##_4_##NW(const GenArgs ap);
-#define SEQ_DECL(NW) SEQ_DECL_V(batch, NW) SEQ_DECL_V(batch, NW##_p) SEQ_DECL_V(flat, NW) SEQ_DECL_V(flat, NW##_p) \
-    extern "C" __global__ void k_seq_keys_##NW(const GenArgs ap); extern "C" __global__ void k_seq_head_##NW(const GenArgs ap); \
-    extern "C" __global__ void k_seq_flush_##NW(const GenArgs ap);
-SEQ_DECL(1) SEQ_DECL(2) SEQ_DECL(3) SEQ_DECL(4)
-// [variant: batch, batch projecting, flat, flat projecting][states - 2][attribute words]
-#define SEQ_ROW(V, N, P) {nullptr, k_seq_##V##_##N##_1##P, k_seq_##V##_##N##_2##P, k_seq_##V##_##N##_3##P, k_seq_##V##_##N##_4##P}
-#define SEQ_TAB(V, P) {SEQ_ROW(V, 2, P), SEQ_ROW(V, 3, P), SEQ_ROW(V, 4, P)}
-static const AbsKernel kSeqBatch[4][3][CHN_MAXNW + 1] = {SEQ_TAB(batch, ), SEQ_TAB(batch, _p), SEQ_TAB(flat, ), SEQ_TAB(flat, _p)};
-static const AbsKernel kSeqKeys[CHN_MAXNW + 1] = {nullptr, k_seq_keys_1, k_seq_keys_2, k_seq_keys_3, k_seq_keys_4};
-static const AbsKernel kSeqHead[CHN_MAXNW + 1] = {nullptr, k_seq_head_1, k_seq_head_2, k_seq_head_3, k_seq_head_4};
-static const AbsKernel kSeqFlush[CHN_MAXNW + 1] = {nullptr, k_seq_flush_1, k_seq_flush_2, k_seq_flush_3, k_seq_flush_4};
-#define ABSF_DECL(NW) extern "C" __global__ void k_abs_flush_##NW(const GenArgs ap);
-ABSF_DECL(1) ABSF_DECL(2) ABSF_DECL(3) ABSF_DECL(4) ABSF_DECL(5) ABSF_DECL(6) ABSF_DECL(7) ABSF_DECL(8)
-static const AbsKernel kAbsFlush[ABS_MAXNW + 1] = {nullptr, k_abs_flush_1, k_abs_flush_2, k_abs_flush_3, k_abs_flush_4,
-                                                   k_abs_flush_5, k_abs_flush_6, k_abs_flush_7, k_abs_flush_8};
-static const AbsKernel kCntFlush[ABS_MAXNW + 1] = {nullptr, k_cnt_flush_1, k_cnt_flush_2, k_cnt_flush_3, k_cnt_flush_4,
-                                                   k_cnt_flush_5, k_cnt_flush_6, k_cnt_flush_7, k_cnt_flush_8};
-#define ABS4_DECL(NW) extern "C" __global__ void k_abs_batchf4_##NW(const GenArgs ap); \
-    extern "C" __global__ void k_abs_timers4_##NW(const GenArgs ap);
-ABS4_DECL(1) ABS4_DECL(2) ABS4_DECL(3)
-static const AbsKernel kAbsBatchF4[4] = {nullptr, k_abs_batchf4_1, k_abs_batchf4_2, k_abs_batchf4_3};
-static const AbsKernel kAbsTimers4[4] = {nullptr, k_abs_timers4_1, k_abs_timers4_2, k_abs_timers4_3};
-static const AbsKernel kAbsTimers[ABS_MAXNW + 1] = {nullptr, k_abs_timers_1, k_abs_timers_2, k_abs_timers_3,
-                                                    k_abs_timers_4, k_abs_timers_5, k_abs_timers_6, k_abs_timers_7,
-                                                    k_abs_timers_8};
-extern "C" __global__ void k_gen_timers(const GenArgs ap);
-extern "C" __global__ void k_cnt_split(const GenArgs a);
-extern "C" __global__ void k_gen_deadlines(const GenArgs ap);
+// A kernel that takes GenArgs (616 B) by value in its kernel arguments, with its symbol name: sg_engine_describe prints
+// the name of what was launched, so an entry and its name come from one token.
+struct GenK {
+    void (*fn)(const GenArgs);
+    const char* name;
+};
+#define GK_DECL(S) extern "C" __global__ void S(const GenArgs ap);
+#define GK_ENT(S) {S, #S},
+// a family's kernels by suffix: attribute words of the event (1..8, 1..4, 1..3), chain states - 1 x kept words,
+// sequence states x attribute words
+#define GK_NW3(X, P, S) X(P##1##S) X(P##2##S) X(P##3##S)
+#define GK_NW4(X, P, S) GK_NW3(X, P, S) X(P##4##S)
+#define GK_NW8(X, P, S) GK_NW4(X, P, S) X(P##5##S) X(P##6##S) X(P##7##S) X(P##8##S)
+#define GK_CHN(X, P, S) GK_NW3(X, P, _0) GK_NW3(X, P, _1) GK_NW3(X, P, _2)
+#define GK_SEQ(X, P, S) GK_NW4(X, P##2_, S) GK_NW4(X, P##3_, S) GK_NW4(X, P##4_, S)
+// one family: its declarations and its table (by attribute words: [0] unused)
+#define GK_TABLE(T, LIST, P, S) LIST(GK_DECL, P, S) static const GenK T[] = {{nullptr, nullptr}, LIST(GK_ENT, P, S)};
+GK_TABLE(kAbsBatch, GK_NW8, k_abs_batch_, )
+GK_TABLE(kAbsBatchF, GK_NW8, k_abs_batchf_, )
+GK_TABLE(kAbsBatchF4, GK_NW3, k_abs_batchf4_, )
+GK_TABLE(kAbsTimers, GK_NW8, k_abs_timers_, )
+GK_TABLE(kAbsTimers4, GK_NW3, k_abs_timers4_, )
+GK_TABLE(kAbsFlush, GK_NW8, k_abs_flush_, )
+GK_TABLE(kAbsdBatch, GK_NW8, k_absd_batch_, )
+GK_TABLE(kAbsdBatchF, GK_NW8, k_absd_batchf_, )
+GK_TABLE(kAbsdTimers, GK_NW8, k_absd_timers_, )
+GK_TABLE(kAbsdTimersF, GK_NW8, k_absd_timersf_, )
+GK_TABLE(kAbsdFlush, GK_NW8, k_absd_flush_, )
+GK_TABLE(kCntBatch, GK_NW8, k_cnt_batch_, )
+GK_TABLE(kCntFlush, GK_NW8, k_cnt_flush_, )
+GK_TABLE(kChnBatch, GK_CHN, k_chn_batch_, )   // [1 + 3 * kept words + (states - 2)]
+GK_TABLE(kChnWide, GK_CHN, k_chn_wide_, )     // (over the keys the chain kernel handed over)
+GK_TABLE(kSeqBatch, GK_SEQ, k_seq_batch_, )   // [1 + 4 * (states - 2) + (attribute words - 1)]
+GK_TABLE(kSeqBatchP, GK_SEQ, k_seq_batch_, _p)
+GK_TABLE(kSeqFlat, GK_SEQ, k_seq_flat_, )
+GK_TABLE(kSeqFlatP, GK_SEQ, k_seq_flat_, _p)
+GK_TABLE(kSeqKeys, GK_NW4, k_seq_keys_, )
+GK_TABLE(kSeqHead, GK_NW4, k_seq_head_, )
+GK_TABLE(kSeqFlush, GK_NW4, k_seq_flush_, )
+GK_DECL(k_gen_batch) GK_DECL(k_gen_timers) GK_DECL(k_gen_deadlines) GK_DECL(k_cnt_split)
 extern "C" __global__ void k_gen_due(const int64_t* nd, uint32_t K, int64_t now, uint32_t* due,
                                      unsigned long long* ndue);
 extern "C" __global__ void k_gen_collapse(const unsigned long long* key, const uint32_t* li, uint64_t n,
@@ -1368,7 +1327,38 @@ struct TimerLess {
 // ---------------------------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------------------------
+// One launch of a push or of an advance.  A stage's workgroups are fixed when the route is resolved, except where the
+// batch decides them.
+enum { GEN_G_FIXED = 0, GEN_G_KPL = 1, GEN_G_ELEMS = 2 };
+struct GenStage {
+    GenK k;
+    const char* note;   // what sg_engine_describe prints in parentheses after the kernel's name
+    uint32_t gridBy;    // GEN_G_FIXED: `grid` workgroups; GEN_G_KPL: one lane per GEN_KPL keys; GEN_G_ELEMS: one workgroup
+    uint32_t grid;      // per `grid` elements of the batch
+    uint32_t block, lds;
+    bool rows;          // it writes a counter row per workgroup, which k_gen_stats_reduce sums afterwards
+    uint32_t mode;      // GenArgs.mode (GEN_M_*)
+    // its place in the hand-over chain: it appends the keys it cannot hold to list `hand` (where the walk has that
+    // many) and reads the keys that list `hand` - 1 holds
+    int hand;
+};
+enum GenFamily { GEN_F_GENERAL, GEN_F_ABS, GEN_F_CNT, GEN_F_CHN, GEN_F_SEQ, GEN_F_SEQ_FLAT };
+// What a push and an advance of this engine launch, in order (gen_route).
+struct GenRoute {
+    GenFamily family = GEN_F_GENERAL;
+    bool pay = false;     // the push kernels read the key-sorted payload with every attribute word of the event
+    bool emits = true;    // a push emits matches, which are ordered after its last stage
+    std::vector<GenStage> push, adv;
+    GenK flushRec{}, flushDeep{};   // gen_flush_deep: the register-window records, the deep store
+    size_t flushDeepLds = 0;
+};
+// the hand-over lists of a walk: every stage but the last appends to one (stages of one place share it)
+static int gen_lists(const std::vector<GenStage>& w) { return w.empty() ? 0 : w.back().hand; }
+struct GenEngine;
+static GenRoute gen_route(const GenEngine* e);
+
 struct GenEngine {
+    GenRoute route;   // resolved by gen_create and gen_set_projection
     // gen_keep_timer_heads: the last advance's emitting keys in head order and their heads (host copies)
     bool keep_heads = false;
     std::vector<uint32_t> head_keys;
@@ -1695,6 +1685,7 @@ GenEngine* gen_create(const uint32_t* ir, size_t nw, const sg_config& cfg, hipSt
         e->out.MC = G.MC;
         e->out.recWords = e->recWords;
         e->out.err = e->err;
+        e->route = gen_route(e);
         GH_OK(hipStreamSynchronize(stream));  // the zeroed state and counters are in place before a push
         return e;
     } catch (...) {
@@ -1713,9 +1704,6 @@ static size_t type_size(int t) {
     }
 }
 
-// the kernels take GenArgs (616 B) by value in their kernel arguments
-enum { GEN_L_BATCH = 0, GEN_L_TIMERS = 1, GEN_L_DEADLINES = 2, GEN_L_ABS_BATCH = 3, GEN_L_ABS_TIMERS = 4, GEN_L_CNT_BATCH = 5,
-       GEN_L_ABSD_BATCH = 6, GEN_L_ABSD_TIMERS = 7, GEN_L_CHN_BATCH = 8, GEN_L_CHN_WIDE = 9, GEN_L_SEQ_BATCH = 10, GEN_L_SEQ_FLAT = 11 };
 // the general kernels over the keys a register-window kernel handed over: a fixed grid striding the list
 #define GEN_FB_BLOCKS 1024u
 // timer sweeps: a fixed grid of one-wave blocks striding over the due keys (their number is on the device)
@@ -1729,105 +1717,133 @@ static uint32_t gen_kpl(uint32_t K) {
     return 1u;
 }
 
-// the register-window kernels of abs_kernels.hip run this query (the shape, and no device projection: the
-// selector items are evaluated by the general kernel's projectSelect)
-static bool abs_on(const GenEngine* e) {
-    return e->host.absOk && e->host.projN == 0 && e->fb_list && e->tstage && e->keyorder;
-}
-// the wave-per-key kernels of absd_kernels.hip take the keys the register window hands over (their LDS slice:
-// one key's lists, partial_capacity entries of 20 + 4 NW bytes, within 64 KB); SG_NO_ABSD: A/B against the
-// general kernels (same results)
-static size_t absd_lds(const GenEngine* e) {   // the key's lists (+ the f1 keys of the FF kernels), its timer queue
+// the wave-per-key kernels' LDS slice: one key's lists (+ the f1 keys of the FF kernels), partial_capacity entries of
+// 20 + 4 NW bytes, and its timer queue
+static size_t absd_lds(const GenEngine* e) {
     const size_t kb = ((size_t)e->host.L * (20u + 4u * e->host.absNW) + 7) & ~(size_t)7;
     return ((kb + 20 * (size_t)e->host.L + 7) & ~(size_t)7) + 8 * (size_t)e->host.Q;
 }
-static bool absd_on(const GenEngine* e) { return e->fb2_list && absd_lds(e) <= 65536; }
 
-// the register-window kernel of cnt_kernels.hip runs this query (the shape, no device projection)
-static bool cnt_on(const GenEngine* e) { return e->host.cntOk && e->host.projN == 0 && e->fb_list; }
-// the chain kernel of chn_kernels.hip runs this query (the shape, no device projection)
-static bool chn_on(const GenEngine* e) { return e->host.chnOk && e->host.projN == 0 && e->fb_list; }
-// the stencil kernels of seq_kernels.hip run this query (the shape, no device projection or one they evaluate from the
-// match's window, their records): the partitioned one (key ids fit the element tags) or the flat one
-static bool seq_any(const GenEngine* e) {
-    return e->host.seqOk && (e->host.projN == 0 || e->host.seqProj) && e->fb_list && e->rec && e->ekey;
+// Which kernels a push and an advance launch, in what order and with what mode bits.  Everything read here is fixed
+// by gen_create except the projection (gen_set_projection resolves the route again); what a batch decides (the fused
+// grouping, the payload width, the grid of a kernel over the batch's elements) stays with gen_push.
+static GenRoute gen_route(const GenEngine* e) {
+    const GenProgram& G = e->host;
+    const uint32_t NW = G.absNW, byKeys = (e->K + 63) / 64, byList = GEN_FB_BLOCKS;
+    const bool noProj = G.projN == 0;
+    auto stage = [](GenK k, const char* note, uint32_t grid, uint32_t mode, int hand, bool rows = false, size_t lds = 0) {
+        return GenStage{k, note, GEN_G_FIXED, grid, 64u, (uint32_t)lds, rows, mode, hand};
+    };
+    const GenK genBatch{k_gen_batch, "k_gen_batch"}, genTimers{k_gen_timers, "k_gen_timers"};
+    GenRoute r;
+    // (a specialised kernel evaluates no device projection, except the select list the stencil kernels evaluate from
+    // the match's window; the key ids of the partitioned stencil kernel fit its element tags)
+    const bool seq = G.seqOk && (noProj || G.seqProj) && e->fb_list && e->rec && e->ekey;
+    if (G.absOk && noProj && e->fb_list && e->tstage && e->keyorder) {
+        // the register-window kernel; the deep keys it hands over, one wave each (SG_NO_ABSD: none; their LDS slice
+        // within 64 KB); what those cannot hold, the general kernel.  An absent state emits nothing on events (its
+        // processAndReturn returns nothing: its matches come from the timers), so a push orders no output.
+        r.family = GEN_F_ABS;
+        r.emits = false;
+        const GenPre &f0 = G.pre[G.absP0], &f1 = G.pre[G.absP1];
+        // both filters are decoded compares (GenPre.ff): the kernel variants without the interpreter
+        const bool ff = (f0.flen == 0 || f0.ff.on) && (f1.flen == 0 || f1.ff.on);
+        // the occupancy-4 build when the launch's waves fit the chip at 4 per SIMD but not at 3
+        const bool occ4 = e->abs_occ4 && NW <= 3 && byKeys > 12u * e->ncu && byKeys <= 16u * e->ncu;
+        const bool absd = e->fb2_list && absd_lds(e) <= 65536;
+        int h = 0;
+        r.push.push_back(stage(ff ? (occ4 ? kAbsBatchF4 : kAbsBatchF)[NW] : kAbsBatch[NW], "register window, lane per key",
+                               byKeys, 0u, h, true));
+        r.adv.push_back(stage((occ4 ? kAbsTimers4 : kAbsTimers)[NW], "register window", byKeys, 0u, h++, true));
+        if (absd) {   // (SG_NO_ABSD_CHUNK: the per-event walk only)
+            r.push.push_back(stage((ff ? kAbsdBatchF : kAbsdBatch)[NW], "deep keys, wave per key", byList,
+                                   e->absd_nochunk ? GEN_M_NOCHUNK : 0u, h, false, absd_lds(e)));
+            r.adv.push_back(stage((ff ? kAbsdTimersF : kAbsdTimers)[NW], "deep keys", byList, GEN_M_NOPAIRS, h++, false,
+                                  absd_lds(e)));
+        }
+        r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST, h));
+        r.adv.push_back(stage(genTimers, "keys handed over", byList, GEN_M_NOPAIRS, h));
+    } else if (G.cntOk && noProj && e->fb_list) {
+        // the register-window kernel, then the general kernel over the keys it handed over (whole runs); this shape
+        // emits at most one match per event
+        r.family = GEN_F_CNT;
+        r.push.push_back(stage(kCntBatch[NW], "register window, lane per key", byKeys, GEN_M_TFIRST, 0, true));
+        r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST | GEN_M_TFIRST, 1));
+    } else if (seq && !G.seqFlat && e->K < SEQ_KEYMASK) {
+        // one lane per key (adopt / hand over, the element tags), the stencil kernel (one thread per element with an
+        // n - 1 halo per workgroup), then the general kernel over the keys whose state was not adopted (whole runs)
+        r.family = GEN_F_SEQ;
+        GenStage st = stage((noProj ? kSeqBatch : kSeqBatchP)[1 + 4 * (G.seqN - 2) + (NW - 1)],
+                            noProj ? "stencil, thread per event" : "stencil, thread per event, select list projected",
+                            256u - ((uint32_t)G.seqN - 1u), GEN_M_TFIRST, 0, true);
+        st.gridBy = GEN_G_ELEMS;
+        st.block = 256u;
+        r.push.push_back(stage(kSeqKeys[NW], "lane per key", byKeys, GEN_M_TFIRST, 0));
+        r.push.push_back(st);
+        r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST | GEN_M_TFIRST, 1));
+    } else if (seq && G.seqFlat && e->K == 1) {
+        // one wave for key 0 (adopt / hand over, the record to read), the flat stencil kernel over the batch as it
+        // arrived, then the general kernel when key 0's state was not adopted
+        r.family = GEN_F_SEQ_FLAT;
+        GenStage st = stage((noProj ? kSeqFlat : kSeqFlatP)[1 + 4 * (G.seqN - 2) + (NW - 1)],
+                            noProj ? "flat stencil, thread per event" : "flat stencil, thread per event, select list projected",
+                            256u - ((uint32_t)G.seqN - 1u), GEN_M_TFIRST, 0, true);
+        st.gridBy = GEN_G_ELEMS;
+        st.block = 256u;
+        r.push.push_back(stage(kSeqHead[NW], "one wave", 1u, GEN_M_TFIRST, 0));
+        r.push.push_back(st);
+        r.push.push_back(stage(genBatch, "key 0 handed over", byList, GEN_M_KEYLIST | GEN_M_TFIRST, 1));
+    } else if (G.chnOk && noProj && e->fb_list) {
+        // the chain kernel; the keys it handed over in the wide window (from the event where each stopped); what that
+        // cannot hold, the general kernel
+        r.family = GEN_F_CHN;
+        const uint32_t i = 1u + 3u * G.chnKW + ((uint32_t)G.chnN - 2u);
+        int h = 0;
+        r.push.push_back(stage(kChnBatch[i], "chained states, register window, lane per key", byKeys, 0u, h++, true));
+        if (G.chnWide && e->fb2_list)
+            r.push.push_back(stage(kChnWide[i], "the keys handed over, wide window", std::min(byList, byKeys), 0u, h++, true));
+        r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST, h));
+    } else {
+        GenStage st = stage(genBatch, "general interpreter, lane per key", 0u, 0u, 0);
+        st.gridBy = GEN_G_KPL;
+        r.push.push_back(st);
+    }
+    r.pay = r.family != GEN_F_GENERAL && r.family != GEN_F_SEQ_FLAT;
+    if (r.adv.empty() && G.nStartup > 0)   // (no absent state: an advance only moves the clock)
+        r.adv.push_back(stage(genTimers, "general interpreter", G.partitioned ? std::min(byKeys, GEN_TIMER_BLOCKS) : 1u, 0u, 0));
+    if (e->deep && e->fb2_list && absd_lds(e) <= 65536) {
+        r.flushDeep = kAbsdFlush[NW];
+        r.flushDeepLds = absd_lds(e);
+    }
+    if (e->rec) r.flushRec = G.seqOk ? kSeqFlush[NW] : G.cntOk ? kCntFlush[NW] : kAbsFlush[NW];
+    return r;
 }
-static bool seq_on(const GenEngine* e) { return seq_any(e) && !e->host.seqFlat && e->K < SEQ_KEYMASK; }
-static bool seq_flat_on(const GenEngine* e) { return seq_any(e) && e->host.seqFlat && e->K == 1; }
-static bool chn_wide_on(const GenEngine* e) { return chn_on(e) && e->host.chnWide && e->fb2_list; }
-// the kernels that read the key-sorted payload with every attribute word of the event
-static bool pay_on(const GenEngine* e) { return abs_on(e) || cnt_on(e) || chn_on(e) || seq_on(e); }
 
-// both filters of the absent-tail shape are decoded compares (GenPre.ff): the kernel variants without the interpreter
-static bool abs_ff(const GenEngine* e) {
-    const GenPre& f0 = e->host.pre[e->host.absP0];
-    const GenPre& f1 = e->host.pre[e->host.absP1];
-    return (f0.flen == 0 || f0.ff.on) && (f1.flen == 0 || f1.ff.on);
-}
-
-static void launch_gen(GenEngine* e, GenArgs a, int which) {
-    const uint32_t blocks = (e->K + 63) / 64;
+// One stage of a push (adv = false) or of an advance: the list it appends to and the list it reads set in its
+// arguments (an advance's lists take no start positions, and its later stages read theirs as the due keys), then the
+// kernel and, where it wrote counter rows, their sum.
+static void launch_gen(GenEngine* e, GenArgs& a, const std::vector<GenStage>& walk, size_t i, bool adv) {
+    const GenStage& s = walk[i];
     a.kpl = gen_kpl(e->K);
+    a.mode = s.mode;
+    if (s.hand < gen_lists(walk)) {
+        if (s.hand == 0) a.fb_list = e->fb_list, a.fb_n = e->fb_n, a.fb_start = adv ? nullptr : e->fb_start;
+        else a.fb2_list = e->fb2_list, a.fb2_n = e->fb2_n, a.fb2_start = adv ? nullptr : e->fb2_start;
+    }
+    if (s.hand > 0) {
+        uint32_t* list = s.hand == 1 ? e->fb_list : e->fb2_list;
+        unsigned long long* n = s.hand == 1 ? e->fb_n : e->fb2_n;
+        if (adv) a.t.due = list, a.t.ndue = n;
+        else a.fb_list = list, a.fb_n = n, a.fb_start = s.hand == 1 ? e->fb_start : e->fb2_start;
+    }
+    const uint32_t wg = s.gridBy == GEN_G_ELEMS ? (a.b.n + s.grid - 1u) / s.grid
+                        : s.gridBy == GEN_G_KPL ? (e->K + 64u * a.kpl - 1) / (64u * a.kpl) : s.grid;
     const GenArgs& ap = a;   // (by value in the kernel arguments: no upload per launch)
-    hipEvent_t t0 = (e->timing && which != GEN_L_DEADLINES) ? e->ev() : nullptr;
-    const bool fb = (a.mode & (GEN_M_KEYLIST | GEN_M_NOPAIRS)) != 0;
-    if (which == GEN_L_TIMERS)
-        hipLaunchKernelGGL(k_gen_timers, dim3(fb ? GEN_FB_BLOCKS : e->host.partitioned ? std::min(blocks, GEN_TIMER_BLOCKS) : 1u),
-                           dim3(64), 0, e->stream, ap);
-    else if (which == GEN_L_DEADLINES) hipLaunchKernelGGL(k_gen_deadlines, dim3(blocks), dim3(64), 0, e->stream, ap);
-    else if (which == GEN_L_ABSD_BATCH || which == GEN_L_ABSD_TIMERS) {
-        // one wave per handed-over key (a fixed grid striding over the list, whose length is on the device); the
-        // variant without the interpreter when both filters are decoded compares
-        const bool ff = abs_ff(e);
-        const AbsKernel k = which == GEN_L_ABSD_BATCH ? (ff ? kAbsdBatchF : kAbsdBatch)[e->host.absNW]
-                                                       : (ff ? kAbsdTimersF : kAbsdTimers)[e->host.absNW];
-        hipLaunchKernelGGL(k, dim3(GEN_FB_BLOCKS), dim3(64), (unsigned)absd_lds(e), e->stream, ap);
-    }
-    else if (which == GEN_L_CHN_BATCH) {   // one lane per key, then the waves' counter rows
-        hipLaunchKernelGGL(kChnBatch[e->host.chnN - 2][e->host.chnKW], dim3(blocks), dim3(64), 0, e->stream, ap);
-        hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((blocks + 1023) / 1024, 16u)), dim3(256),
-                           0, e->stream, e->wstats, blocks, e->stats);
-    }
-    else if (which == GEN_L_SEQ_BATCH) {
-        // one lane per key (adopt / hand over, the element tags), one thread per element with an n - 1 halo per
-        // workgroup, then the workgroups' counter rows
-        const uint32_t NW = e->host.absNW, T = 256u - ((uint32_t)e->host.seqN - 1u), wg = (a.b.n + T - 1u) / T;
-        hipLaunchKernelGGL(kSeqKeys[NW], dim3(blocks), dim3(64), 0, e->stream, ap);
-        hipLaunchKernelGGL(kSeqBatch[e->host.projN ? 1 : 0][e->host.seqN - 2][NW], dim3(wg), dim3(256), 0, e->stream, ap);
+    hipEvent_t t0 = e->timing ? e->ev() : nullptr;
+    hipLaunchKernelGGL(s.k.fn, dim3(wg), dim3(s.block), s.lds, e->stream, ap);
+    if (s.rows)
         hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((wg + 1023) / 1024, 16u)), dim3(256), 0,
                            e->stream, e->wstats, wg, e->stats);
-    }
-    else if (which == GEN_L_SEQ_FLAT) {
-        // one wave for key 0 (adopt / hand over, the record to read), one thread per event of the batch as it arrived
-        // (its count in the arguments) with an n - 1 halo per workgroup, then the workgroups' counter rows
-        const uint32_t NW = e->host.absNW, T = 256u - ((uint32_t)e->host.seqN - 1u), wg = (a.b.n + T - 1u) / T;
-        hipLaunchKernelGGL(kSeqHead[NW], dim3(1), dim3(64), 0, e->stream, ap);
-        hipLaunchKernelGGL(kSeqBatch[e->host.projN ? 3 : 2][e->host.seqN - 2][NW], dim3(wg), dim3(256), 0, e->stream, ap);
-        hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((wg + 1023) / 1024, 16u)), dim3(256), 0,
-                           e->stream, e->wstats, wg, e->stats);
-    }
-    else if (which == GEN_L_CHN_WIDE) {   // a fixed grid striding the hand-over list (its length is on the device)
-        const uint32_t wb = std::min<uint32_t>(GEN_FB_BLOCKS, blocks);
-        hipLaunchKernelGGL(kChnWide[e->host.chnN - 2][e->host.chnKW], dim3(wb), dim3(64), 0, e->stream, ap);
-        hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, 1), dim3(256), 0, e->stream, e->wstats, wb, e->stats);
-    }
-    else if (which == GEN_L_ABS_BATCH || which == GEN_L_ABS_TIMERS || which == GEN_L_CNT_BATCH) {
-        // one lane per key / possible due slot (the due count is on the device); then the waves' counter rows
-        // (the absent kernel's variant for decoded-compare filters when both of its filters are; the occupancy-4
-        // build when the launch's waves fit the chip at 4 per SIMD but not at 3)
-        const bool ff = abs_ff(e);
-        const uint32_t NW = e->host.absNW;
-        const bool occ4 = e->abs_occ4 && NW <= 3 && blocks > 12u * e->ncu && blocks <= 16u * e->ncu;
-        const unsigned lds = 0;
-        hipLaunchKernelGGL(which == GEN_L_ABS_BATCH   ? (ff ? (occ4 ? kAbsBatchF4[NW] : kAbsBatchF[NW]) : kAbsBatch[NW])
-                           : which == GEN_L_CNT_BATCH ? kCntBatch[NW]
-                                                      : (occ4 ? kAbsTimers4[NW] : kAbsTimers[NW]),
-                           dim3(blocks), dim3(64), lds, e->stream, ap);
-        hipLaunchKernelGGL(k_gen_stats_reduce, dim3(GST_N, std::min<uint32_t>((blocks + 1023) / 1024, 16u)), dim3(256),
-                           0, e->stream, e->wstats, blocks, e->stats);
-    }
-    else hipLaunchKernelGGL(k_gen_batch, dim3(fb ? GEN_FB_BLOCKS : (e->K + 64u * a.kpl - 1) / (64u * a.kpl)), dim3(64), 0,
-                            e->stream, ap);
     GH_OK(hipGetLastError());
     if (t0) e->spans.push_back({t0, e->ev(), 1});
 }
@@ -1842,6 +1858,35 @@ static uint32_t sgd_max_key(const uint32_t* k, uint32_t n, bool skip_null) {
     return m;
 }
 
+// a push's matches in the reference's order
+static void gen_order(GenEngine* e, const GenArgs& a, uint32_t n) {
+    // order: the batch's base + the exclusive prefix of the per-trigger counts + rank (k_gen_tsum / k_gen_tscan /
+    // k_gen_order; the counts are reset by k_gen_order)
+    const uint32_t nt = (n + GEN_OT - 1) / GEN_OT, nsup = (nt + GEN_OST - 1) / GEN_OST;
+    hipLaunchKernelGGL(k_gen_tsum, dim3(nsup), dim3(1024), 0, e->stream, e->t_cnt, n, e->tile_pre, e->sup_sum);
+    hipLaunchKernelGGL(k_gen_tscan, dim3(1), dim3(1024), 0, e->stream, e->sup_sum, nsup, e->sup_off, e->out.count, e->obase);
+    const uint64_t maxRaw = e->rawCap;
+    const unsigned scat_grid = (unsigned)std::min<uint64_t>((maxRaw + 255) / 256, 1024);
+    if (a.mode & GEN_M_TFIRST) {
+        // output-major gather of the one match per trigger; a trigger of a handed-over key that emitted several
+        // (t_multi, set on the device) turns it off and every record is placed by (t_off, rank) instead
+        hipLaunchKernelGGL(k_gen_order<true>, dim3(nt), dim3(256), 0, e->stream, e->raw, e->t_cnt, e->t_off, e->t_first,
+                           e->tile_pre, e->sup_off, n, e->out, (const uint32_t*)e->t_multi,
+                           (const unsigned long long*)e->obase);
+        hipLaunchKernelGGL(k_gen_scatter, dim3(scat_grid), dim3(256), 0, e->stream, e->raw, e->raw_count,
+                           e->rawCap / GEN_RAWSEG, (uint32_t)GEN_RAWSEG, e->t_off, e->out, (const uint32_t*)e->t_multi,
+                           (const unsigned long long*)e->obase);
+    } else {
+        hipLaunchKernelGGL(k_gen_order<false>, dim3(nt), dim3(256), 0, e->stream, e->raw, e->t_cnt, e->t_off, e->t_first,
+                           e->tile_pre, e->sup_off, n, e->out, (const uint32_t*)e->t_multi,
+                           (const unsigned long long*)e->obase);
+        hipLaunchKernelGGL(k_gen_scatter, dim3((unsigned)std::min<uint64_t>((maxRaw + 255) / 256, 4096)), dim3(256), 0,
+                           e->stream, e->raw, e->raw_count, e->rawCap / GEN_RAWSEG, (uint32_t)GEN_RAWSEG, e->t_off, e->out,
+                           (const uint32_t*)nullptr, (const unsigned long long*)e->obase);
+    }
+    GH_OK(hipGetLastError());
+}
+
 int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
     const GenProgram& G = e->host;
     (void)hipGetLastError();   // (a stale error of an unrelated earlier call on this thread: rocPRIM reads it)
@@ -1853,6 +1898,7 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
     if (e->held) { msg = "release the polled matches before pushing"; return SG_ERR_STATE; }
     const uint32_t n = (uint32_t)b->n;
     const bool dev = b->mem == SG_MEM_DEVICE;
+    const GenRoute& r = e->route;
     GenArgs a = e->args();
     a.b.n = n;
     a.b.stream = b->stream;
@@ -1883,8 +1929,8 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
         cl.add(e->seg_end, (size_t)e->K * 4);
         cl.add(e->raw_count, 8 * GEN_RAWSEG);
         cl.add(e->t_multi, 4);
-        if (pay_on(e) || seq_flat_on(e)) cl.add(e->fb_n, 8);
-        if ((abs_on(e) && absd_on(e)) || chn_wide_on(e)) cl.add(e->fb2_n, 8);
+        if (gen_lists(r.push) >= 1) cl.add(e->fb_n, 8);
+        if (gen_lists(r.push) >= 2) cl.add(e->fb2_n, 8);
         GH_OK(cl.launch(e->stream));
     }
     if (G.partitioned) {
@@ -1906,7 +1952,7 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
         PackSrc ps{};
         uint32_t W = 0;
         bool nul = false;
-        if (pay_on(e)) {
+        if (r.pay) {
             const int st = (int)b->stream;
             for (int c = 0; c < G.nattr[st] && W <= 4; c++) {
                 const int t = G.attrType[st][c];
@@ -1944,7 +1990,7 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
         // the register-window kernels' batches (count, absent): grouped by 64-key tile (two 7-bit passes), then split by key per tile
         // (k_cnt_split), instead of three 8-bit passes; while a batch has shown a tile of more than 2^14 events (one
         // wave splits a tile), the sorted grouping
-        const bool fused = e->cnt_fused && !e->cnt_skewed && pay_on(e) && W >= 1 && W <= 4;
+        const bool fused = e->cnt_fused && !e->cnt_skewed && r.pay && W >= 1 && W <= 4;
         e->cnt_fused_last = fused;
         if (fused) {
             ga.W = W;
@@ -1967,7 +2013,7 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
             a.b.tile_lo = nullptr;
             a.b.tpay = nullptr;
             a.b.tileMax = nullptr;
-        } else if (pay_on(e) && W >= 1 && W <= 4) {
+        } else if (r.pay && W >= 1 && W <= 4) {
             ga.W = W;
             ga.src = ps;
             ga.out = e->pay;
@@ -1996,112 +2042,15 @@ int gen_push(GenEngine* e, const sg_batch* b, std::string& msg) {
     if (e->timing)  // sg_stats.live_at_batch_start (outside the batch kernel's span)
         hipLaunchKernelGGL(k_gen_live, dim3((e->K + 255) / 256), dim3(256), 0, e->stream, e->dprog, e->state, e->K,
                            e->stats + GST_LIVE0, (const uint32_t*)e->rec, e->seg_begin, e->seg_end);
-    if (abs_on(e)) {
-        // the register-window kernel, then the general kernel over the keys it handed over; this shape
-        // emits nothing on events (an absent state's processAndReturn returns nothing; its matches come
-        // from the timers), so there is no batch ordering
-        a.fb_list = e->fb_list;
-        a.fb_n = e->fb_n;
-        a.fb_start = e->fb_start;
-        launch_gen(e, a, GEN_L_ABS_BATCH);
-        if (absd_on(e)) {  // the deep keys, one wave each; what they cannot hold goes on to the general kernel
-            a.fb2_list = e->fb2_list;
-            a.fb2_n = e->fb2_n;
-            a.fb2_start = e->fb2_start;
-            const uint32_t m0 = a.mode;
-            if (e->absd_nochunk) a.mode |= GEN_M_NOCHUNK;   // (SG_NO_ABSD_CHUNK: the per-event walk only)
-            launch_gen(e, a, GEN_L_ABSD_BATCH);
-            a.mode = m0;
-            a.fb_list = e->fb2_list;
-            a.fb_n = e->fb2_n;
-            a.fb_start = e->fb2_start;
-        }
-        a.mode = GEN_M_KEYLIST;
-        launch_gen(e, a, GEN_L_BATCH);
-        GH_OK(hipGetLastError());
-        e->st.events += n;
-        e->st.batches++;
-        e->st.advance_launches++;
-        if (!dev) GH_OK(hipStreamSynchronize(e->stream));
-        return SG_OK;
-    }
-    if (cnt_on(e)) {
-        // the register-window kernel, then the general kernel over the keys it handed over (whole runs);
-        // both write raw records + per-trigger counts, ordered below
-        a.fb_list = e->fb_list;
-        a.fb_n = e->fb_n;
-        a.fb_start = e->fb_start;
-        a.mode = GEN_M_TFIRST;   // (this shape emits at most one match per event)
-        launch_gen(e, a, GEN_L_CNT_BATCH);
-        a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
-    } else if (seq_on(e)) {
-        // the stencil kernel, then the general kernel over the keys whose state it could not adopt (whole runs)
-        a.fb_list = e->fb_list;
-        a.fb_n = e->fb_n;
-        a.fb_start = e->fb_start;
-        a.b.ekey = e->ekey;
-        a.mode = GEN_M_TFIRST;   // (this shape emits at most one match per event)
-        launch_gen(e, a, GEN_L_SEQ_BATCH);
-        a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
-    } else if (seq_flat_on(e)) {
-        // the flat stencil kernel over the batch as it arrived; the general kernel when key 0's state was not adopted
-        a.fb_list = e->fb_list;
-        a.fb_n = e->fb_n;
-        a.fb_start = e->fb_start;
-        a.b.ekey = e->ekey;
-        a.mode = GEN_M_TFIRST;
-        launch_gen(e, a, GEN_L_SEQ_FLAT);
-        a.mode = GEN_M_KEYLIST | GEN_M_TFIRST;
-    } else if (chn_on(e)) {
-        // the chain kernel, then the general kernel over the keys it handed over (from the event where each stopped)
-        a.fb_list = e->fb_list;
-        a.fb_n = e->fb_n;
-        a.fb_start = e->fb_start;
-        launch_gen(e, a, GEN_L_CHN_BATCH);
-        if (chn_wide_on(e)) {   // the keys it handed over, in the wide window; what that cannot hold goes on
-            a.fb2_list = e->fb2_list;
-            a.fb2_n = e->fb2_n;
-            a.fb2_start = e->fb2_start;
-            launch_gen(e, a, GEN_L_CHN_WIDE);
-            a.fb_list = e->fb2_list;
-            a.fb_n = e->fb2_n;
-            a.fb_start = e->fb2_start;
-        }
-        a.mode = GEN_M_KEYLIST;
-    }
-    launch_gen(e, a, GEN_L_BATCH);
-    // order: the batch's base + the exclusive prefix of the per-trigger counts + rank (k_gen_tsum / k_gen_tscan /
-    // k_gen_order; the counts are reset by k_gen_order)
-    const uint32_t nt = (n + GEN_OT - 1) / GEN_OT, nsup = (nt + GEN_OST - 1) / GEN_OST;
-    hipLaunchKernelGGL(k_gen_tsum, dim3(nsup), dim3(1024), 0, e->stream, e->t_cnt, n, e->tile_pre, e->sup_sum);
-    hipLaunchKernelGGL(k_gen_tscan, dim3(1), dim3(1024), 0, e->stream, e->sup_sum, nsup, e->sup_off, e->out.count, e->obase);
-    const uint64_t maxRaw = e->rawCap;
-    const unsigned scat_grid = (unsigned)std::min<uint64_t>((maxRaw + 255) / 256, 1024);
-    if (a.mode & GEN_M_TFIRST) {
-        // output-major gather of the one match per trigger; a trigger of a handed-over key that emitted several
-        // (t_multi, set on the device) turns it off and every record is placed by (t_off, rank) instead
-        hipLaunchKernelGGL(k_gen_order<true>, dim3(nt), dim3(256), 0, e->stream, e->raw, e->t_cnt, e->t_off, e->t_first,
-                           e->tile_pre, e->sup_off, n, e->out, (const uint32_t*)e->t_multi,
-                           (const unsigned long long*)e->obase);
-        hipLaunchKernelGGL(k_gen_scatter, dim3(scat_grid), dim3(256), 0, e->stream, e->raw, e->raw_count,
-                           e->rawCap / GEN_RAWSEG, (uint32_t)GEN_RAWSEG, e->t_off, e->out, (const uint32_t*)e->t_multi,
-                           (const unsigned long long*)e->obase);
-    } else {
-        hipLaunchKernelGGL(k_gen_order<false>, dim3(nt), dim3(256), 0, e->stream, e->raw, e->t_cnt, e->t_off, e->t_first,
-                           e->tile_pre, e->sup_off, n, e->out, (const uint32_t*)e->t_multi,
-                           (const unsigned long long*)e->obase);
-        hipLaunchKernelGGL(k_gen_scatter, dim3((unsigned)std::min<uint64_t>((maxRaw + 255) / 256, 4096)), dim3(256), 0,
-                           e->stream, e->raw, e->raw_count, e->rawCap / GEN_RAWSEG, (uint32_t)GEN_RAWSEG, e->t_off, e->out,
-                           (const uint32_t*)nullptr, (const unsigned long long*)e->obase);
-    }
-    GH_OK(hipGetLastError());
+    if (r.family == GEN_F_SEQ || r.family == GEN_F_SEQ_FLAT) a.b.ekey = e->ekey;
+    for (size_t i = 0; i < r.push.size(); i++) launch_gen(e, a, r.push, i, false);
+    if (r.emits) gen_order(e, a, n);
     e->st.events += n;
     e->st.batches++;
     e->st.advance_launches++;
     if (!dev) GH_OK(hipStreamSynchronize(e->stream));
     return SG_OK;
 }
-
 bool gen_keep_timer_heads(GenEngine* e, bool keep) {
     e->keep_heads = keep && e->keyorder;
     return e->keyorder;
@@ -2134,8 +2083,8 @@ int gen_advance(GenEngine* e, int64_t t, std::string& msg) {
         cl.add(e->raw_count, 8);
         cl.add(e->nvalid, 8);
         cl.add(e->tm.ndue, 8);
-        if (abs_on(e)) cl.add(e->fb_n, 8);
-        if (abs_on(e) && absd_on(e)) cl.add(e->fb2_n, 8);
+        if (gen_lists(e->route.adv) >= 1) cl.add(e->fb_n, 8);
+        if (gen_lists(e->route.adv) >= 2) cl.add(e->fb2_n, 8);
         if (e->keyorder) cl.add(e->ctr, 32);
         GH_OK(cl.launch(e->stream));
     }
@@ -2145,26 +2094,7 @@ int gen_advance(GenEngine* e, int64_t t, std::string& msg) {
     }
     a.o.nseg = 1;
     a.o.seg_cap = e->rawCap;
-    if (abs_on(e)) {  // the register-window sweep, then the general sweep over the keys it handed over
-        a.fb_list = e->fb_list;
-        a.fb_n = e->fb_n;
-        a.fb_start = nullptr;
-        launch_gen(e, a, GEN_L_ABS_TIMERS);
-        a.mode = GEN_M_NOPAIRS;
-        a.t.due = e->fb_list;
-        a.t.ndue = e->fb_n;
-        if (absd_on(e)) {
-            a.fb2_list = e->fb2_list;
-            a.fb2_n = e->fb2_n;
-            a.fb2_start = nullptr;
-            launch_gen(e, a, GEN_L_ABSD_TIMERS);
-            a.t.due = e->fb2_list;
-            a.t.ndue = e->fb2_n;
-        }
-        launch_gen(e, a, GEN_L_TIMERS);
-    } else {
-        launch_gen(e, a, GEN_L_TIMERS);
-    }
+    for (size_t i = 0; i < e->route.adv.size(); i++) launch_gen(e, a, e->route.adv, i, true);
     if (e->keyorder) {  // the A.10 check and the keys with matches, before the one host round trip
         const uint32_t blocks = std::min<uint32_t>((e->K + GEN_TPREP_BLOCK - 1) / GEN_TPREP_BLOCK, 1024u);
         hipLaunchKernelGGL(k_timer_prep, dim3(blocks), dim3(GEN_TPREP_BLOCK), 0, e->stream, e->tm.dpair_key,
@@ -2423,6 +2353,7 @@ int gen_set_projection(GenEngine* e, const uint32_t* code, uint32_t words, const
     e->out.projOff = G.projOff;
     GH_OK(hipStreamSynchronize(e->stream));  // no kernel reads the program while it changes
     GH_OK(hipMemcpy(e->dprog, &G, sizeof(GenProgram), hipMemcpyHostToDevice));
+    e->route = gen_route(e);
     return SG_OK;
 }
 
@@ -2500,46 +2431,15 @@ uint64_t gen_min_seq(GenEngine* e) {
     return h;
 }
 
-// the kernels a push and an advance dispatch (sg_engine_describe), in launch order
+// the kernels a push and an advance dispatch (sg_engine_describe), in launch order: the route's names and notes
 std::string gen_describe(const GenEngine* e) {
-    const GenProgram& G = e->host;
-    const std::string nw = std::to_string(G.absNW);
-    std::string push, adv;
-    if (abs_on(e)) {
-        const GenPre& f0 = G.pre[G.absP0];
-        const GenPre& f1 = G.pre[G.absP1];
-        const bool ff = (f0.flen == 0 || f0.ff.on) && (f1.flen == 0 || f1.ff.on);
-        const uint32_t blocks = (e->K + 63) / 64;
-        const bool occ4 = e->abs_occ4 && G.absNW <= 3 && blocks > 12u * e->ncu && blocks <= 16u * e->ncu;
-        push = (ff ? (occ4 ? "k_abs_batchf4_" : "k_abs_batchf_") : "k_abs_batch_") + nw + " (register window, lane per key)";
-        adv = (occ4 ? "k_abs_timers4_" : "k_abs_timers_") + nw + " (register window)";
-        if (absd_on(e)) {
-            push += (ff ? " + k_absd_batchf_" : " + k_absd_batch_") + nw + " (deep keys, wave per key)";
-            adv += (ff ? " + k_absd_timersf_" : " + k_absd_timers_") + nw + " (deep keys)";
-        }
-        push += " + k_gen_batch (keys handed over)";
-        adv += " + k_gen_timers (keys handed over)";
-    } else if (cnt_on(e)) {
-        push = "k_cnt_batch_" + nw + " (register window, lane per key) + k_gen_batch (keys handed over)";
-    } else if (seq_on(e)) {
-        push = "k_seq_keys_" + nw + " (lane per key) + k_seq_batch_" + std::to_string(G.seqN) + "_" + nw + (G.projN ? "_p" : "") +
-               (G.projN ? " (stencil, thread per event, select list projected)" : " (stencil, thread per event)") +
-               " + k_gen_batch (keys handed over)";
-    } else if (seq_flat_on(e)) {
-        push = "k_seq_head_" + nw + " (one wave) + k_seq_flat_" + std::to_string(G.seqN) + "_" + nw + (G.projN ? "_p" : "") +
-               (G.projN ? " (flat stencil, thread per event, select list projected)" : " (flat stencil, thread per event)") +
-               " + k_gen_batch (key 0 handed over)";
-    } else if (chn_on(e)) {
-        push = "k_chn_batch_" + std::to_string(G.chnN - 1) + "_" + std::to_string(G.chnKW) +
-               " (chained states, register window, lane per key) + " +
-               (chn_wide_on(e) ? "k_chn_wide_" + std::to_string(G.chnN - 1) + "_" + std::to_string(G.chnKW) +
-                                     " (the keys handed over, wide window) + "
-                               : std::string()) +
-               "k_gen_batch (keys handed over)";
-    } else {
-        push = "k_gen_batch (general interpreter, lane per key)";
-        if (G.nStartup > 0) adv = "k_gen_timers (general interpreter)";
-    }
+    auto walk = [](const std::vector<GenStage>& w) {
+        std::string s;
+        for (const GenStage& st : w) s += (s.empty() ? "" : " + ") + std::string(st.k.name) + " (" + st.note + ")";
+        return s;
+    };
+    std::string push = walk(e->route.push);
+    const std::string adv = walk(e->route.adv);
     if (e->cnt_fused_last)
         push = "k_part_hist + k_part_scan + k_part_scatter x2 + k_tile_bounds (grouping by 64-key tile) + k_cnt_split "
                "(key split per tile); " + push;
@@ -2588,19 +2488,13 @@ static bool gen_outputs_pending(GenEngine* e) {
 // every key whose lists live in the deep store (GEN_W0_DEEP) written back to its block: before anything reads
 // the blocks' lists on the host or in a kernel that does not know the deep store
 void gen_flush_deep(GenEngine* e, bool rec) {
-    if (e->rec && rec) {   // the register-window kernels' records
-        GenArgs a = e->args();
-        const GenArgs& ap = a;
-        hipLaunchKernelGGL(e->host.seqOk ? kSeqFlush[e->host.absNW]
-                           : e->host.cntOk ? kCntFlush[e->host.absNW] : kAbsFlush[e->host.absNW], dim3((e->K + 63) / 64),
-                           dim3(64), 0, e->stream, ap);
-        GH_OK(hipGetLastError());
-    }
-    if (!e->deep || !absd_on(e)) return;
-    GenArgs a = e->args();
-    const GenArgs& ap = a;
-    hipLaunchKernelGGL(kAbsdFlush[e->host.absNW], dim3(std::min<uint32_t>(e->K, 4096u)), dim3(64),
-                       (unsigned)absd_lds(e), e->stream, ap);
+    const GenRoute& r = e->route;
+    const GenArgs a = e->args();
+    if (r.flushRec.fn && rec)   // the register-window kernels' records
+        hipLaunchKernelGGL(r.flushRec.fn, dim3((e->K + 63) / 64), dim3(64), 0, e->stream, a);
+    if (r.flushDeep.fn && e->deep)
+        hipLaunchKernelGGL(r.flushDeep.fn, dim3(std::min<uint32_t>(e->K, 4096u)), dim3(64), (unsigned)r.flushDeepLds,
+                           e->stream, a);
     GH_OK(hipGetLastError());
 }
 
@@ -2621,7 +2515,12 @@ int gen_restore(GenEngine* e, const uint32_t* words, const GenClock& clk, std::s
     if (e->held) { msg = "release the polled matches before a restore"; return SG_ERR_STATE; }
     if (gen_outputs_pending(e)) { msg = "poll the emitted matches before a restore"; return SG_ERR_STATE; }
     GH_OK(hipMemcpyAsync(e->state, words, gen_state_words(e) * 4, hipMemcpyHostToDevice, e->stream));
-    if (e->tm.nd) launch_gen(e, e->args(), GEN_L_DEADLINES);  // the timers' due index from the restored state
+    if (e->tm.nd) {  // the timers' due index from the restored state
+        GenArgs a = e->args();
+        a.kpl = gen_kpl(e->K);
+        hipLaunchKernelGGL(k_gen_deadlines, dim3((e->K + 63) / 64), dim3(64), 0, e->stream, a);
+        GH_OK(hipGetLastError());
+    }
     GH_OK(hipStreamSynchronize(e->stream));
     e->now = clk.now;
     e->lastEventTs = clk.last_event_ts;
