@@ -64,7 +64,7 @@ namespace {
 constexpr int CHN_NW = CHN_MAXNW;   // attribute words of an event (pack.h Pay<W>, W <= 4; chn_shape checks absNW)
 constexpr uint32_t CHN_ORD_MASK = 0xffffffu;   // order stamp: low 24 bits of ord[]; the kept words' null bits above
 
-template <int NE, int KW, int RR> struct ChnKey {
+template <int NE, int KW, int RR, bool PROJ> struct ChnKey {
     static constexpr int R = RR;
     static constexpr int XW = (NE + 1) / 2;   // 16-bit pool entries, two per word
     const cGenProgram& G;
@@ -452,6 +452,89 @@ template <int NE, int KW, int RR> struct ChnKey {
         stamp = n;
     }
 
+    // ---- PROJ: the select list of a match, evaluated by the lane that emits it ----
+    // The walk keeps of a captured event only the words later filters read (kw); a select item may read any
+    // attribute of any state.  A window of the match's NE + 1 events would cost up to 5 * (NE + 1) registers the walk
+    // does not have (247 of 256 at three states), a staging area in LDS a wave per CU.  So an item's operand is
+    // fetched where it is read: attribute `a` of state t of the match of the partial in slot j, one or two words and
+    // a null bit, from wherever that event is now —
+    //   the trigger (t = NE): the event's registers, by selects;
+    //   captured in this batch, its pool entry deferred (canonOK, 0x8000 | d): element runB + d of the key-sorted
+    //       payload (pack.h Pay<W>: position, attribute words, null bits when present, ts offset);
+    //   captured in this batch into a block that is not canonical (!canonOK, 0xffff): the batch columns at the
+    //       event's position (its seq offset: sqw), as storeEvent reads them;
+    //   else a pool entry (carried in from an earlier push, or written when it was captured): the StreamEvent record
+    //       of the key's block.
+    // These loads (each a sector per lane) sit beside the walk, not in it.
+    __device__ __forceinline__ GVal matchAttr(int j, int t, uint32_t a, const AbsEv<CHN_NW>& ev) const {
+        const int ty = G.attrType[0][a];
+        const bool wide = ty == SG_T_LONG || ty == SG_T_DOUBLE;
+        const uint32_t o = G.absOff[a];
+        uint32_t lo = 0, hi = 0, nb = 0;
+        if (t == NE) {
+#pragma unroll
+            for (int q = 0; q < CHN_NW; ++q) {
+                lo = (uint32_t)q == o ? ev.w[q] : lo;
+                hi = (uint32_t)q == o + 1 ? ev.w[q] : hi;
+            }
+            nb = (ev.nb >> a) & 1u;
+        } else {
+            const uint32_t h = getIx(j, t);
+            if (canonOK && (h & 0x8000u)) {
+                const uint32_t st = A.b.payStride;
+                const gu32* p = gp(A.b.pay) + (size_t)(runB + (h & 0x7fffu)) * st;
+                lo = p[1u + o];
+                if (wide) hi = p[2u + o];
+                if (A.b.payNull) nb = (p[st - 2u] >> a) & 1u;
+            } else if (!canonOK && h == 0xffffu) {
+                const uint32_t pos = sqw(j, t);
+                const void* c = A.b.col[a];
+                if (wide) {
+                    const uint64_t v = gp((const uint64_t*)c)[pos];
+                    lo = (uint32_t)v;
+                    hi = (uint32_t)(v >> 32);
+                } else if (ty == SG_T_BOOL) {
+                    lo = gp((const uint8_t*)c)[pos] ? 1u : 0u;
+                } else {
+                    lo = gp((const uint32_t*)c)[pos];
+                }
+                nb = (A.b.nul[a] && gp(A.b.nul[a])[pos]) ? 1u : 0u;
+            } else if (h < G.SECAP) {
+                lo = W(sew(h, SE_ATTR + 2u * a));
+                if (wide) hi = W(sew(h, SE_ATTR + 2u * a + 1u));
+                nb = (W(sew(h, SE_NULL)) >> a) & 1u;
+            } else {   // (no entry of a live partial's captured event is outside the pool)
+                nb = 1u;
+            }
+        }
+        return GVal{wide ? ((uint64_t)lo | ((uint64_t)hi << 32)) : (uint64_t)lo, nb != 0u};
+    }
+    // the state whose event slot s holds in a match (0 .. NE - 1 captured, NE the trigger), -1: a slot the chain does
+    // not have (single-event slots: index 0 or `last`)
+    __device__ __forceinline__ int matchState(uint32_t s, int32_t c) const {
+        const int t = s < (uint32_t)GEN_MAXSLOT ? G.chnSlotEv[s] : -1;
+        return (t < 0 || t > NE || !(c == 0 || c == -1)) ? -1 : t;
+    }
+    // the items as gen_kernels.hip projectSelect lays them out: 3 words each (value lo, hi, null) from pv; `having`
+    // reads the items just written (SG_PROJ_SLOT_OUT).  No aggregators, every item at most two entries deep
+    // (gen_host.hip gen_set_projection checked it)
+    __device__ __forceinline__ void project(int j, const AbsEv<CHN_NW>& ev, gu32* pv) {
+        for (uint32_t i = 0; i < G.projN; i++) {   // (a run-time loop: one copy of the interpreter)
+            const GVal v = jo_eval<false>(G.code, G.projPc[i], G.projLen[i], err,
+                                          [&](uint32_t s, uint32_t a, int32_t c) -> GVal {
+                                              if (s == SG_PROJ_SLOT_OUT)
+                                                  return GVal{(uint64_t)pv[3 * a] | ((uint64_t)pv[3 * a + 1] << 32),
+                                                              pv[3 * a + 2] != 0};
+                                              const int t = matchState(s, c);
+                                              return t < 0 ? GVal{0, true} : matchAttr(j, t, a, ev);
+                                          },
+                                          [&](uint32_t s, int32_t c) -> bool { return matchState(s, c) < 0; });
+            pv[3 * i] = (uint32_t)v.b;
+            pv[3 * i + 1] = (uint32_t)(v.b >> 32);
+            pv[3 * i + 2] = v.null ? 1u : 0u;
+        }
+    }
+
     // ---- the matches of the last state's partials `H` on this event: one raw record each, in list order
     __device__ __forceinline__ void emit(uint32_t H, const AbsEv<CHN_NW>& ev, uint32_t pos) {
         const uint32_t c = __popc(H);
@@ -489,6 +572,7 @@ template <int NE, int KW, int RR> struct ChnKey {
             }
             seqs[2 * sid(NE)] = (uint32_t)ev.seq;
             seqs[2 * sid(NE) + 1] = (uint32_t)(ev.seq >> 32);
+            if constexpr (PROJ) project(j, ev, rec + G.projOff);
         }
         matches += c;
         gp(A.o.t_cnt)[pos] = c;
@@ -863,13 +947,13 @@ __device__ __forceinline__ void chn_gather(const GenArgs& a, const cGenProgram& 
 // ---- batch: one lane per key walks its events of the key-sorted batch ----
 // ---- one key's run [b, e) of the key-sorted batch by one lane: false = handed over at `stop` (the general kernel,
 // or the wide window, continues from the event where it stopped; stop = b: the block is not this kernel's)
-template <int NE, int KW, int RR> struct ChnRun {
+template <int NE, int KW, int RR, bool PROJ> struct ChnRun {
     unsigned long long scanned = 0, created = 0, matches = 0, keys = 0;
     uint32_t err = 0;
     bool fb = false;
     uint32_t stop = 0;
     __device__ __forceinline__ void run(const GenArgs& a, uint32_t key, uint32_t b, uint32_t e, uint32_t* cold) {
-        ChnKey<NE, KW, RR> L(a, key);
+        ChnKey<NE, KW, RR, PROJ> L(a, key);
         L.cold = cold;
         L.runB = b;
         bool walk = b < e;
@@ -916,7 +1000,7 @@ template <int NE, int KW, int RR> struct ChnRun {
 };
 
 // ---- batch: one lane per key walks its events of the key-sorted batch ----
-template <int NE, int KW> __device__ __forceinline__ void chn_batch(const GenArgs& a) {
+template <int NE, int KW, bool PROJ> __device__ __forceinline__ void chn_batch(const GenArgs& a) {
     constexpr int R = CHN_R(NE + 1);
     const uint32_t key = blockIdx.x * 64u + threadIdx.x;
     uint32_t b = 0, e = 0;
@@ -925,7 +1009,7 @@ template <int NE, int KW> __device__ __forceinline__ void chn_batch(const GenArg
         e = gp(a.b.seg_end)[key];
     }
     __shared__ uint32_t cold[R * (NE + (NE + 1) / 2) * 64];
-    ChnRun<NE, KW, R> r;
+    ChnRun<NE, KW, R, PROJ> r;
     r.run(a, key < a.K ? key : 0u, b, e, cold);
     abs_fallback(a, r.fb, key, r.stop);
     abs_wave_stats(a, r.scanned, r.created, r.matches, r.keys, r.err, r.fb ? 1ull : 0ull);
@@ -935,10 +1019,10 @@ template <int NE, int KW> __device__ __forceinline__ void chn_batch(const GenArg
 // fixed grid of waves striding the list (its length is on the device), each key from the event where it stopped;
 // what this window cannot hold goes on to the general kernel (fb2).  Its hand-overs are not counted again as
 // window spills.
-template <int NE, int KW> __device__ __forceinline__ void chn_wide(const GenArgs& a) {
+template <int NE, int KW, bool PROJ> __device__ __forceinline__ void chn_wide(const GenArgs& a) {
     constexpr int R = CHN_RW(NE + 1);
     __shared__ uint32_t cold[R * (NE + (NE + 1) / 2) * 64];
-    ChnRun<NE, KW, R> r;
+    ChnRun<NE, KW, R, PROJ> r;
     const unsigned long long n = *a.fb_n;
     for (unsigned long long base = (unsigned long long)blockIdx.x * 64u; base < n;
          base += (unsigned long long)gridDim.x * 64u) {   // (wave-uniform)
@@ -975,34 +1059,25 @@ template <int NE, int KW> __device__ __forceinline__ void chn_wide(const GenArgs
 #ifndef SG_CHN_WAVES
 #define SG_CHN_WAVES 2
 #endif
-#define CHN_KERNEL(NE, KW)                                                                                          \
+// S / PROJ: the `_p` instantiations evaluate the select list in the lane that emits a match (ChnKey::project); the
+// others compile from the same code without it
+#define CHN_KERNEL(NE, KW, S, PROJ)                                                                                 \
     extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SG_CHN_WAVES, 8)))          \
-    k_chn_batch_##NE##_##KW(const GenArgs ap) {                                                                     \
+    k_chn_batch_##NE##_##KW##S(const GenArgs ap) {                                                                  \
         (void)ap;   /* (read through the kernarg segment: a reference to the by-value parameter copies it to scratch) */ \
-        chn_batch<NE, KW>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());                    \
+        chn_batch<NE, KW, PROJ>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());              \
     }
-CHN_KERNEL(1, 0)
-CHN_KERNEL(1, 1)
-CHN_KERNEL(1, 2)
-CHN_KERNEL(2, 0)
-CHN_KERNEL(2, 1)
-CHN_KERNEL(2, 2)
-CHN_KERNEL(3, 0)
-CHN_KERNEL(3, 1)
-CHN_KERNEL(3, 2)
 // the wide window: one wave per SIMD (up to 512 VGPRs)
-#define CHN_WIDE_KERNEL(NE, KW)                                                                                     \
+#define CHN_WIDE_KERNEL(NE, KW, S, PROJ)                                                                            \
     extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8)))                     \
-    k_chn_wide_##NE##_##KW(const GenArgs ap) {                                                                      \
+    k_chn_wide_##NE##_##KW##S(const GenArgs ap) {                                                                   \
         (void)ap;                                                                                                   \
-        chn_wide<NE, KW>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());                     \
+        chn_wide<NE, KW, PROJ>(*(const GenArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr());               \
     }
-CHN_WIDE_KERNEL(1, 0)
-CHN_WIDE_KERNEL(1, 1)
-CHN_WIDE_KERNEL(1, 2)
-CHN_WIDE_KERNEL(2, 0)
-CHN_WIDE_KERNEL(2, 1)
-CHN_WIDE_KERNEL(2, 2)
-CHN_WIDE_KERNEL(3, 0)
-CHN_WIDE_KERNEL(3, 1)
-CHN_WIDE_KERNEL(3, 2)
+#define CHN_SHAPES(X, S, PROJ)                                                                                      \
+    X(1, 0, S, PROJ) X(1, 1, S, PROJ) X(1, 2, S, PROJ) X(2, 0, S, PROJ) X(2, 1, S, PROJ) X(2, 2, S, PROJ)           \
+    X(3, 0, S, PROJ) X(3, 1, S, PROJ) X(3, 2, S, PROJ)
+CHN_SHAPES(CHN_KERNEL, , false)
+CHN_SHAPES(CHN_WIDE_KERNEL, , false)
+CHN_SHAPES(CHN_KERNEL, _p, true)
+CHN_SHAPES(CHN_WIDE_KERNEL, _p, true)

@@ -198,9 +198,11 @@ struct GenProgram {
     // (gen_host.hip chn_shape): chnP[i] the processor of state i, chnEvery: `every` re-arms p0's seed; the attribute
     // words later filters read of a captured event are kept in the window (chnKW of them: event word chnKeepW[c] of
     // attribute chnKeepA[c]; chnAttrK[a] = the kept index of attribute a's first word, or -1) and chnSlotEv[s] is
-    // the event index (state) whose event slot s holds
+    // the event index (state) whose event slot s holds; chnProj: the select list set by sg_set_projection is one the
+    // `_p` kernels evaluate in the lane that emits the match (the rule of seqProj)
     int32_t chnOk, chnN, chnEvery, chnKW;
     int32_t chnWide;   // the wide-window kernel takes the keys the chain kernel hands over (its window fits the block)
+    int32_t chnProj;
     int32_t chnP[4];
     uint32_t chnKeepW[2], chnKeepA[2];
     int32_t chnAttrK[GEN_MAXA];

@@ -42,7 +42,7 @@ struct GenK {
 #define GK_NW3(X, P, S) X(P##1##S) X(P##2##S) X(P##3##S)
 #define GK_NW4(X, P, S) GK_NW3(X, P, S) X(P##4##S)
 #define GK_NW8(X, P, S) GK_NW4(X, P, S) X(P##5##S) X(P##6##S) X(P##7##S) X(P##8##S)
-#define GK_CHN(X, P, S) GK_NW3(X, P, _0) GK_NW3(X, P, _1) GK_NW3(X, P, _2)
+#define GK_CHN(X, P, S) GK_NW3(X, P, _0##S) GK_NW3(X, P, _1##S) GK_NW3(X, P, _2##S)
 #define GK_SEQ(X, P, S) GK_NW4(X, P##2_, S) GK_NW4(X, P##3_, S) GK_NW4(X, P##4_, S)
 // one family: its declarations and its table (by attribute words: [0] unused)
 #define GK_TABLE(T, LIST, P, S) LIST(GK_DECL, P, S) static const GenK T[] = {{nullptr, nullptr}, LIST(GK_ENT, P, S)};
@@ -61,6 +61,8 @@ GK_TABLE(kCntBatch, GK_NW8, k_cnt_batch_, )
 GK_TABLE(kCntFlush, GK_NW8, k_cnt_flush_, )
 GK_TABLE(kChnBatch, GK_CHN, k_chn_batch_, )   // [1 + 3 * kept words + (states - 2)]
 GK_TABLE(kChnWide, GK_CHN, k_chn_wide_, )     // (over the keys the chain kernel handed over)
+GK_TABLE(kChnBatchP, GK_CHN, k_chn_batch_, _p)
+GK_TABLE(kChnWideP, GK_CHN, k_chn_wide_, _p)
 GK_TABLE(kSeqBatch, GK_SEQ, k_seq_batch_, )   // [1 + 4 * (states - 2) + (attribute words - 1)]
 GK_TABLE(kSeqBatchP, GK_SEQ, k_seq_batch_, _p)
 GK_TABLE(kSeqFlat, GK_SEQ, k_seq_flat_, )
@@ -409,7 +411,7 @@ void cnt_shape(GenProgram& G) {
 // Anything else stays on the general kernels.
 void chn_shape(GenProgram& G) {
     G.chnOk = 0;
-    G.chnWide = 0;
+    G.chnWide = G.chnProj = 0;
     const int n = G.nprocs;
     if (G.qtype != SG_Q_PATTERN || !G.partitioned || G.nstreams != 1 || n < 2 || n > CHN_MAXN || G.nslots != n ||
         G.nStartup != 0 || G.MC != 1 || G.nAll != n)
@@ -1737,7 +1739,8 @@ static GenRoute gen_route(const GenEngine* e) {
     const GenK genBatch{k_gen_batch, "k_gen_batch"}, genTimers{k_gen_timers, "k_gen_timers"};
     GenRoute r;
     // (a specialised kernel evaluates no device projection, except the select list the stencil kernels evaluate from
-    // the match's window; the key ids of the partitioned stencil kernel fit its element tags)
+    // the match's window and the chain kernels from wherever the match's events are; the key ids of the partitioned
+    // stencil kernel fit its element tags)
     const bool seq = G.seqOk && (noProj || G.seqProj) && e->fb_list && e->rec && e->ekey;
     if (G.absOk && noProj && e->fb_list && e->tstage && e->keyorder) {
         // the register-window kernel; the deep keys it hands over, one wave each (SG_NO_ABSD: none; their LDS slice
@@ -1793,15 +1796,22 @@ static GenRoute gen_route(const GenEngine* e) {
         r.push.push_back(stage(kSeqHead[NW], "one wave", 1u, GEN_M_TFIRST, 0));
         r.push.push_back(st);
         r.push.push_back(stage(genBatch, "key 0 handed over", byList, GEN_M_KEYLIST | GEN_M_TFIRST, 1));
-    } else if (G.chnOk && noProj && e->fb_list) {
+    } else if (G.chnOk && (noProj || G.chnProj) && e->fb_list) {
         // the chain kernel; the keys it handed over in the wide window (from the event where each stopped); what that
-        // cannot hold, the general kernel
+        // cannot hold, the general kernel (which projects its own matches: a key handed over mid-run has its earlier
+        // matches projected by the chain kernels and its later ones by the interpreter, in one poll)
         r.family = GEN_F_CHN;
         const uint32_t i = 1u + 3u * G.chnKW + ((uint32_t)G.chnN - 2u);
         int h = 0;
-        r.push.push_back(stage(kChnBatch[i], "chained states, register window, lane per key", byKeys, 0u, h++, true));
+        r.push.push_back(stage((noProj ? kChnBatch : kChnBatchP)[i],
+                               noProj ? "chained states, register window, lane per key"
+                                      : "chained states, register window, lane per key, select list projected",
+                               byKeys, 0u, h++, true));
         if (G.chnWide && e->fb2_list)
-            r.push.push_back(stage(kChnWide[i], "the keys handed over, wide window", std::min(byList, byKeys), 0u, h++, true));
+            r.push.push_back(stage((noProj ? kChnWide : kChnWideP)[i],
+                                   noProj ? "the keys handed over, wide window"
+                                          : "the keys handed over, wide window, select list projected",
+                                   std::min(byList, byKeys), 0u, h++, true));
         r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST, h));
     } else {
         GenStage st = stage(genBatch, "general interpreter, lane per key", 0u, 0u, 0);
@@ -2271,6 +2281,22 @@ int gen_poll(GenEngine* e, uint32_t mem, sg_match_batch* out, std::string& msg) 
     return SG_OK;
 }
 
+// a projection the sequence and chain kernels evaluate in the thread that emits the match: no aggregators, every
+// item at most two entries deep and without ifThenElse (jo_eval<false>, as seq_terms asks of the filters), reading the
+// stream's own attributes
+static bool proj_in_lane(const GenProgram& G) {
+    if (G.projAgg != 0) return false;
+    for (uint32_t i = 0; i < G.projN; i++) {
+        const int d = prog_depth(G.code, G.projPc[i], G.projLen[i]);
+        if (d < 0 || d > 2) return false;
+        for (uint32_t w = G.projPc[i]; w < G.projPc[i] + G.projLen[i]; w += (uint32_t)sg_op_len(G.code[w] & 0xffu))
+            if ((G.code[w] & 0xffu) == SG_OP_VAR && ((G.code[w] >> 16) & 0xffu) != SG_PROJ_SLOT_OUT &&
+                G.code[w + 1] >= (uint32_t)G.nattr[0])
+                return false;
+    }
+    return true;
+}
+
 int gen_set_projection(GenEngine* e, const uint32_t* code, uint32_t words, const uint32_t* pc, const uint32_t* len,
                        const uint32_t* types, uint32_t n, std::string& msg) {
     GenProgram& G = e->host;
@@ -2326,17 +2352,9 @@ int gen_set_projection(GenEngine* e, const uint32_t* code, uint32_t words, const
     G.ncode += words;
     G.projN = n;
     G.projAgg = A;
-    // the sequence kernels project from the match's window: no aggregators, every item at most two entries deep and
-    // without ifThenElse (jo_eval<false>, as seq_terms asks of the filters), reading the stream's own attributes
-    G.seqProj = G.seqOk && A == 0;
-    for (uint32_t i = 0; i < n && G.seqProj; i++) {
-        const int d = prog_depth(G.code, G.projPc[i], G.projLen[i]);
-        if (d < 0 || d > 2) G.seqProj = 0;
-        for (uint32_t w = G.projPc[i]; w < G.projPc[i] + G.projLen[i]; w += (uint32_t)sg_op_len(G.code[w] & 0xffu))
-            if ((G.code[w] & 0xffu) == SG_OP_VAR && ((G.code[w] >> 16) & 0xffu) != SG_PROJ_SLOT_OUT &&
-                G.code[w + 1] >= (uint32_t)G.nattr[0])
-                G.seqProj = 0;
-    }
+    const bool inLane = proj_in_lane(G);
+    G.seqProj = G.seqOk && inLane;
+    G.chnProj = G.chnOk && inLane;
     G.projOff = e->recWords;
     e->recWords += 3 * (S + H);
     if (A) {  // the aggregators' per-key state joins the key blocks (no push yet: all zero)

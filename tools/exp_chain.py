@@ -1,10 +1,18 @@
-"""P3 (3-state chain) at bench size through the engine: events/s, the chain kernel's hand-overs (window_spills) and
-keys, for rocprofv3 kernel traces of the chain kernel against the general kernel (SG_NO_CHN=1).
+"""P3 (3-state chain) at bench size through the engine: 2^20 keys, 2^22-event batches resident in HBM, steady state (the
+first pushes fill the 10-second `within` window — 2.1 s of stream time each — and are not timed), step time per push
+and events/s with the spread over the timed pushes, the chain kernel's hand-overs (window_spills) and the work
+counters.  SG_NO_CHN=1 runs the same query on the general kernel; rocprofv3 wraps this script for kernel traces.
 
-    python tools/exp_chain.py [steps]
+    python tools/exp_chain.py [steps] [warmup] [--projection] [--lib PATH]
+
+--projection  the query's select list set on the device (sg_set_projection), as the runtime does: k_chn_*_p
+--lib PATH    another build of the engine library (a checkout of the parent commit: the baseline of a comparison)
+Only the public engine API is used, so the same script drives either library.
 """
+import argparse
 import importlib
 import os
+import statistics
 import sys
 import time
 
@@ -13,41 +21,46 @@ sys.path.insert(0, ROOT)
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("steps", nargs="?", type=int, default=10)
+    ap.add_argument("warmup", nargs="?", type=int, default=5)
+    ap.add_argument("--projection", action="store_true")
+    ap.add_argument("--lib", default=None)
+    args = ap.parse_args()
     import torch
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 6
     sa = importlib.import_module("siddhi-1_amd")
     synth = importlib.import_module("siddhi-1_amd.synth")
+    cp = importlib.import_module("siddhi-1_amd.compiler")
     K, B = 1 << 20, 1 << 22
-    app = sa.parse_app(synth.P3_QUERY)
-    cq = sa.compile_query(app, app.queries[0], sa.StringDictionary())
+    app, strings = sa.parse_app(synth.P3_QUERY), sa.StringDictionary()
+    cq = sa.compile_query(app, app.queries[0], strings)
     dev = torch.device("cuda", 0)
-    bats = []
-    for s in range(steps):
-        d = synth.stock_ticks(s * B, B, K)
-        bats.append({k: torch.from_numpy(v.view("int32") if v.dtype.kind == "u" else v).to(dev) for k, v in d.items()})
+    bats = [synth.stock_ticks_torch(torch, s * B, B, K, dev) for s in range(args.warmup + args.steps)]
     torch.cuda.synchronize()
-    eng = sa.NativeEngine(sa.load_hip_library(), "sg_", cq.ir, n_keys=K, max_batch=B, partial_capacity=32,
-                          match_capacity=2 * B, device=0)
-    print(eng.describe(), flush=True)
-    t0 = None
-    for s in range(steps):
-        if s == 1:
-            eng.synchronize()
-            t0 = time.perf_counter()
-        t = bats[s]
+    lib = sa.native.load_library(args.lib) if args.lib else sa.load_hip_library()
+    eng = sa.NativeEngine(lib, "sg_", cq.ir, n_keys=K, max_batch=B, partial_capacity=32, match_capacity=2 * B, device=0)
+    if args.projection:
+        eng.set_projection(*cp.projection_program(cq, strings))
+    times = []
+    for s, t in enumerate(bats):
+        eng.synchronize()
+        t0 = time.perf_counter()
         eng.push(0, s * B, (B, t["ts"].data_ptr(), [t["symbol"].data_ptr(), t["price"].data_ptr(), t["volume"].data_ptr()],
                             t["key"].data_ptr()), [0, 1, 2], mem=sa.native.SG_MEM_DEVICE)
         m = eng.poll_device()
         eng.release(m)
-        if os.environ.get("CHN_PER_STEP"):   # (per push: wall time and the counters, the engine synchronised)
-            eng.synchronize()
+        eng.synchronize()
+        if s >= args.warmup:
+            times.append(time.perf_counter() - t0)
+        if os.environ.get("CHN_PER_STEP"):   # (per push: wall time and the counters)
             st = eng.stats()
-            print(f"step {s}: {time.perf_counter() - (t0 or time.perf_counter()):.4f} s, live {st['partials_live']}, "
+            print(f"step {s}: {(time.perf_counter() - t0) * 1e3:.3f} ms, live {st['partials_live']}, "
                   f"spills {st['window_spills']}, matches {st['matches']}", flush=True)
-    eng.synchronize()
-    el = time.perf_counter() - t0
-    st = eng.stats()
-    print(f"P3: {B * (steps - 1) / el:.3e} events/s, {el / (steps - 1) * 1e3:.2f} ms per step; stats {st}", flush=True)
+    print(eng.describe(), flush=True)
+    med = statistics.median(times)
+    what = "select list on the device" if args.projection else "no projection"
+    print(f"P3 ({what}, {args.lib or 'this build'}): {med * 1e3:.3f} ms per step (median of {len(times)}; "
+          f"min {min(times) * 1e3:.3f}, max {max(times) * 1e3:.3f}), {B / med:.3e} events/s; stats {eng.stats()}", flush=True)
     eng.close()
 
 
