@@ -13,7 +13,9 @@
 //                   runs (~16-64 consecutive elements of one digit per chunk: coalesced stores)
 // Uses built on it:
 //   - the two-state C2 path (sgd_group_tiles_fused): two 6-bit passes on the key tile (key >> 8: the 256 keys
-//     of one advance workgroup), elements tagged with key & 255 in the position's top byte; the split by key
+//     of one advance workgroup), elements tagged with key & 255 in the position's top byte; the first pass
+//     writes each element's second digit beside it as one byte and the second pass's scatter writes the tile
+//     starts from the first pass's digit starts (no pass over the sorted batch for them); the split by key
 //     happens inside the advance kernel's LDS staging (p2_jit.hip), so a key-sorted payload never goes through
 //     HBM;
 //   - every other grouping (sgd_group_sorted): LSD passes of <= 8 bits (one pass up to 256 keys), the keys
@@ -43,7 +45,7 @@ struct PartScratch {
     uint32_t* mat;       // [SGD_PT_MAX_DIG * nblk]
     uint32_t* tot;       // [SGD_PT_MAX_DIG]
     uint32_t* lo[2];     // [SGD_PT_MAX_DIG + 1] digit starts of a pass (+ the valid count), two alternating
-    void* keys[2];       // [n] keys (u32 / u64) or u16 tile codes carried through the passes
+    void* keys[2];       // [n] keys (u32 / u64) carried through the passes, or the fused grouping's u8 digits
     void* el[2];         // [n * 6 words] elements between passes
 };
 size_t sgd_part_scratch_bytes(uint64_t max_n);
@@ -73,7 +75,7 @@ hipError_t sgd_group_sorted(const GroupArgs& a, hipStream_t stream);
 // (K <= 2^20, n <= 2^24)
 hipError_t sgd_group_tiles_fused(const GroupArgs& a, uint32_t* tile_lo, hipStream_t stream);
 inline bool sgd_fused_ok(uint64_t K, uint64_t max_batch, uint32_t W, uint32_t tile_bits = SGD_PT_TILE_BITS) {
-    // (tile codes travel as u16: at most 65,535 tiles; SGD_PT_MAX_TILES bounds the C2 advance grid)
+    // (two passes of <= 8 bits on the tile id: at most 65,535 tiles; SGD_PT_MAX_TILES bounds the C2 advance grid)
     const uint64_t max_tiles = tile_bits == SGD_PT_TILE_BITS ? SGD_PT_MAX_TILES : 65535u;
     return K >= 1 && K <= (max_tiles << tile_bits) && max_batch <= SGD_PT_FUSED_MAX_BATCH &&
            W >= 1 && W <= 4;

@@ -14,6 +14,12 @@
 //                   the chunk goes out in that order, each digit's run to its start (the digit totals scanned
 //                   + the row scan), consecutive lanes to consecutive addresses.
 //
+// The fused grouping's second pass also writes the tile starts (k_part_scatter<.., TILES>): its input is sorted by
+// the low tile digit d1, so the events of digit d2 that come before tile (d2, d1) in the output are those before
+// input position lo1[d1] (the first pass's start of d1), and
+//     tile_lo[d2 << b1 | d1] = (start of the chunk's run of d2) + #{events of the chunk of digit d2 before lo1[d1]}
+// in the chunk that lo1[d1] falls into.  Only chunks that hold a boundary (<= 2^b1 of thousands) do the counting.
+//
 // Why staged runs: a lane-scattered store (each lane of a wave store to a different digit's range) is one
 // memory request per lane; measured on a 4096-way single pass (tools/ubench/part_bench), the stores alone took
 // 300 of 500 us per 2^24 events, and a dwordx3 store per element did not help.  With <= 256 digits a chunk's
@@ -30,8 +36,8 @@ namespace {
 
 enum { PT_RANGE = 1, PT_DESC = 2 };
 enum { PT_GATHER = 0, PT_IDX = 1, PT_MOVE = 2 };    // element source
-enum { PD_U32 = 0, PD_U64 = 1, PD_U16 = 2 };        // digit source: keys u32 / u64, or u16 tile codes
-enum { PS_NONE = 0, PS_KEY = 1, PS_CODE = 2 };      // side output: the key, or a u16 code of it
+enum { PD_U32 = 0, PD_U64 = 1, PD_U8 = 2 };         // digit source: keys u32 / u64, or the u8 digits of PS_DIG
+enum { PS_NONE = 0, PS_KEY = 1, PS_DIG = 2 };       // side output: the key, or the next pass's digit of it (u8)
 
 struct PassArgs {
     uint32_t n;               // elements (upper bound)
@@ -41,13 +47,17 @@ struct PassArgs {
     uint32_t mode;            // PT_RANGE: keys >= K are dropped (SG_KEY_NULL silently when drop_null, others
                               // reported in err); PT_DESC: descending digit order
     uint32_t K, drop_null;
-    uint32_t cshift, cmask;   // PS_CODE: code = (key >> cshift) & cmask
+    uint32_t sshift;          // PS_DIG: the digit written beside the elements = key >> sshift (< 256: keys < K)
+    uint32_t bbits;           // TILES: digit bits of the pass before (2^bbits boundaries)
     const void* keys;         // [n] digit source
-    void* side_out;           // [n] keys or codes written beside the elements
+    void* side_out;           // [n] keys or digits written beside the elements
     uint32_t* mat;
     uint32_t* tot;
     uint32_t* lo;             // [ndig + 1]: digit starts, then the valid count (written by chunk 0)
     uint32_t* err;
+    const uint32_t* blo;      // TILES: [2^bbits] digit starts of the pass before (the input's boundaries)
+    uint32_t* tile_lo;        // TILES: [n_tiles + 1] starts of the tiles (this digit << bbits | the digit before)
+    uint32_t n_tiles, pad;
 };
 
 struct ElemArgs {
@@ -60,7 +70,7 @@ struct ElemArgs {
 
 template <int DS> struct DKey { typedef uint32_t T; };
 template <> struct DKey<PD_U64> { typedef uint64_t T; };
-template <> struct DKey<PD_U16> { typedef uint16_t T; };
+template <> struct DKey<PD_U8> { typedef uint8_t T; };
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -179,7 +189,7 @@ __global__ void __launch_bounds__(256) k_part_scan(uint32_t* __restrict__ mat, u
 
 template <int SIDE, class T> struct SideT { typedef uint8_t U; static constexpr uint32_t B = 0; };
 template <class T> struct SideT<PS_KEY, T> { typedef T U; static constexpr uint32_t B = sizeof(T); };
-template <class T> struct SideT<PS_CODE, T> { typedef uint16_t U; static constexpr uint32_t B = 2; };
+template <class T> struct SideT<PS_DIG, T> { typedef uint8_t U; static constexpr uint32_t B = 1; };
 
 template <int S> __device__ __forceinline__ void st_elem(uint32_t* o, const uint32_t* v) {
     if constexpr (S == 3) {
@@ -207,23 +217,32 @@ __host__ __device__ constexpr uint32_t pt_scatter_lds(uint32_t ce, uint32_t S, u
 
 // ---- the stable scatter of one chunk --------------------------------------------------------------
 // per event: digit (8 bits) | wave rank << 8 (9 bits) | key & 255 << 17 | valid << 31
-template <int DS, int SRC, int S, int SIDE, int EPT>
+// TILES (the fused grouping's second pass, no side output): the tile starts a.tile_lo as well, from the boundaries
+// a.blo of the pass before.  Boundary position p belongs to chunk min(p / CE, nblk - 1): a boundary at the end of the
+// input (the valid count, when the last low digits have no events) counts the whole last chunk or none of an empty
+// one, both the digit's end.  Such a chunk keeps each event's index in the chunk beside its element in LDS (where
+// a side output would be); a digit's run is in arrival order, so the events of digit d before the boundary are a
+// prefix of the run, found by bisection, one (boundary, digit) pair per thread.
+template <int DS, int SRC, int S, int SIDE, int EPT, int TILES>
 __global__ void __launch_bounds__(SGD_PT_THREADS) k_part_scatter(const PassArgs a, const ElemArgs e) {
     typedef typename DKey<DS>::T T;
     typedef SideT<SIDE, T> SD;
     constexpr uint32_t CE = SGD_PT_THREADS * EPT, WE = 64u * EPT;
+    constexpr uint32_t SB = TILES ? 2u : SD::B;
     static_assert(WE <= 512u, "wave ranks are 9 bits");
+    static_assert(!TILES || (SIDE == PS_NONE && CE <= 65536u), "the events' u16 indices take the side output's place");
     extern __shared__ uint32_t lds[];
     const uint32_t c = pt_chunk(blockIdx.x, a.nb8);
     if (c >= a.nblk) return;
     const uint32_t ND = a.ndig;
     uint32_t* el_l = lds;                                               // [CE][S] digit-sorted elements
-    typename SD::U* side_l = (typename SD::U*)(el_l + CE * S);          // [CE] their keys / codes
-    uint8_t* dg = (uint8_t*)(el_l + CE * S) + CE * SD::B;               // [CE] their digits
+    typename SD::U* side_l = (typename SD::U*)(el_l + CE * S);          // [CE] their keys / digits
+    uint16_t* li_l = (uint16_t*)(el_l + CE * S);                        // TILES: [CE] their indices in the chunk
+    uint8_t* dg = (uint8_t*)(el_l + CE * S) + CE * SB;                  // [CE] their digits
     uint16_t* wc = (uint16_t*)(dg + CE);                                // [8][ND] per wave: counts, then places
     uint32_t* bst = (uint32_t*)(wc + SGD_PT_WAVES * ND + 2u);           // [ND] digit run starts in the chunk
     uint32_t* gof = bst + ND;                                           // [ND] their global starts
-    uint32_t* ws = gof + ND;                                            // [16] scan scratch; ws[15]: valid events
+    uint32_t* ws = gof + ND;  // [16] scan scratch; ws[8], ws[9]: the chunk's boundaries (TILES); ws[15]: valid events
     const uint32_t tid = threadIdx.x, w = tid >> 6, lane = tid & 63u;
     const uint32_t nv = a.n_dev ? *a.n_dev : a.n;
 
@@ -281,7 +300,25 @@ __global__ void __launch_bounds__(SGD_PT_THREADS) k_part_scatter(const PassArgs 
             }
             ex += v[x];
         }
-        if (c == 0 && lane == 63) a.lo[ND] = incl;
+        if (c == 0 && lane == 63) {
+            a.lo[ND] = incl;
+            if constexpr (TILES) a.tile_lo[a.n_tiles] = incl;
+        }
+    }
+    if constexpr (TILES) {
+        // the boundaries of this chunk: blo is sorted, so they are consecutive (wave 1: first, count)
+        if (w == 1) {
+            const uint32_t NB = 1u << a.bbits;  // <= 256
+            uint32_t first = 0, cnt = 0;
+            for (uint32_t b0 = 0; b0 < NB; b0 += 64u) {  // (uniform trips)
+                const uint32_t b = b0 + lane;
+                const bool in = b < NB && min(a.blo[b] / CE, a.nblk - 1u) == c;
+                const uint64_t m = __ballot(in);
+                if (m && !cnt) first = b0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+                cnt += (uint32_t)__popcll(m);
+            }
+            if (lane == 0) { ws[8] = first; ws[9] = cnt; }
+        }
     }
     for (uint32_t x = tid; x < (SGD_PT_WAVES * ND + 1u) / 2u; x += SGD_PT_THREADS) ((uint32_t*)wc)[x] = 0u;
     __syncthreads();
@@ -332,6 +369,7 @@ __global__ void __launch_bounds__(SGD_PT_THREADS) k_part_scatter(const PassArgs 
     }
     __syncthreads();
 
+    const uint32_t tb_n = TILES ? ws[9] : 0u;  // boundaries of the pass before in this chunk (block-uniform)
     // gather each event's element and place it in LDS, digit-sorted
 #pragma unroll
     for (uint32_t j = 0; j < EPT; ++j) {
@@ -346,7 +384,10 @@ __global__ void __launch_bounds__(SGD_PT_THREADS) k_part_scatter(const PassArgs 
             for (int u = 0; u < S; ++u) el_l[pos * S + u] = el[j][u];
             dg[pos] = (uint8_t)d;
             if constexpr (SIDE == PS_KEY) side_l[pos] = k[j];
-            if constexpr (SIDE == PS_CODE) side_l[pos] = (uint16_t)(((uint64_t)k[j] >> a.cshift) & a.cmask);
+            if constexpr (SIDE == PS_DIG) side_l[pos] = (uint8_t)((uint64_t)k[j] >> a.sshift);
+            if constexpr (TILES) {
+                if (tb_n) li_l[pos] = (uint16_t)(w * WE + j * 64u + lane);
+            }
         }
     }
     __syncthreads();
@@ -362,23 +403,23 @@ __global__ void __launch_bounds__(SGD_PT_THREADS) k_part_scatter(const PassArgs 
         st_elem<S>((uint32_t*)e.out + (size_t)dst * S, v);
         if constexpr (SIDE != PS_NONE) ((typename SD::U*)a.side_out)[dst] = side_l[p];
     }
-}
 
-// ---- the fused grouping's tile starts, from the tile codes of the sorted elements -------------------------------
-// tile_lo[t] = first element of tile t (tiles without events: the next tile's start), tile_lo[n_tiles] = nv
-__global__ void __launch_bounds__(256) k_tile_bounds(const uint16_t* __restrict__ code, const uint32_t* __restrict__ n_dev,
-                                                     uint32_t n_tiles, uint32_t* __restrict__ tile_lo) {
-    const uint32_t nv = *n_dev;
-    const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8u;  // 8 consecutive elements per thread
-    if (i0 > nv) return;
-    int32_t c[9];
-    c[0] = i0 > 0 ? (int32_t)code[i0 - 1] : -1;
-#pragma unroll
-    for (uint32_t q = 0; q < 8; ++q) c[q + 1] = i0 + q < nv ? (int32_t)code[i0 + q] : (int32_t)n_tiles;
-#pragma unroll
-    for (uint32_t q = 0; q < 8; ++q) {
-        if (i0 + q > nv) break;
-        for (int32_t t = c[q] + 1; t <= c[q + 1]; ++t) tile_lo[t] = i0 + q;
+    // tile_lo[d << bbits | b] for the chunk's boundaries b and every digit d: the first element of that tile (tiles
+    // without events: the next tile's start; tile_lo[n_tiles], the valid count, is chunk 0's above)
+    if constexpr (TILES) {
+        for (uint32_t x = tid; x < tb_n * ND; x += SGD_PT_THREADS) {
+            const uint32_t b = ws[8] + x / ND, d = x % ND;
+            const uint32_t t = (d << a.bbits) | b;
+            if (t >= a.n_tiles) continue;
+            const uint32_t th = a.blo[b] - c * CE;  // events of the chunk before the boundary (<= CE)
+            uint32_t lo = bst[d], hi = d + 1u < ND ? bst[d + 1u] : nvc;
+            while (lo < hi) {  // the first event of the run at or past the boundary
+                const uint32_t mid = (lo + hi) >> 1;
+                if (li_l[mid] < th) lo = mid + 1u;
+                else hi = mid;
+            }
+            a.tile_lo[t] = gof[d] + (lo - bst[d]);
+        }
     }
 }
 
@@ -419,7 +460,8 @@ uint32_t nblk_of(uint64_t n, uint32_t S) {
     return (uint32_t)std::max<uint64_t>(1, (n + ce - 1) / ce);
 }
 
-template <int DS, int SRC, int S, int SIDE> hipError_t run_pass(PassArgs a, const ElemArgs& e, hipStream_t st) {
+template <int DS, int SRC, int S, int SIDE, int TILES = 0>
+hipError_t run_pass(PassArgs a, const ElemArgs& e, hipStream_t st) {
     typedef typename DKey<DS>::T T;
     constexpr uint32_t EPT = ept_of(S);
     a.nblk = nblk_of(a.n, S);
@@ -429,17 +471,17 @@ template <int DS, int SRC, int S, int SIDE> hipError_t run_pass(PassArgs a, cons
     if (hipError_t x = hipGetLastError()) return x;
     hipLaunchKernelGGL(k_part_scan, dim3(a.ndig), dim3(256), 0, st, a.mat, a.nblk, a.tot);
     if (hipError_t x = hipGetLastError()) return x;
-    constexpr uint32_t SB = SideT<SIDE, T>::B;
+    constexpr uint32_t SB = TILES ? 2u : SideT<SIDE, T>::B;
     const size_t sl = pt_scatter_lds(SGD_PT_THREADS * EPT, S, SB, a.ndig);
     static bool attr = [] {
-        (void)hipFuncSetAttribute((const void*)k_part_scatter<DS, SRC, S, SIDE, EPT>,
+        (void)hipFuncSetAttribute((const void*)k_part_scatter<DS, SRC, S, SIDE, EPT, TILES>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)pt_scatter_lds(SGD_PT_THREADS * EPT, S, SB, SGD_PT_MAX_DIG));
         (void)hipGetLastError();
         return true;
     }();
     (void)attr;
-    hipLaunchKernelGGL((k_part_scatter<DS, SRC, S, SIDE, EPT>), dim3(grid), dim3(SGD_PT_THREADS), sl, st, a, e);
+    hipLaunchKernelGGL((k_part_scatter<DS, SRC, S, SIDE, EPT, TILES>), dim3(grid), dim3(SGD_PT_THREADS), sl, st, a, e);
     return hipGetLastError();
 }
 
@@ -455,13 +497,14 @@ template <int SIDE> hipError_t run_gather(const PassArgs& a, const ElemArgs& e, 
 }
 
 // a later pass: elements of S words moved
-template <int DS, int SIDE> hipError_t run_move(const PassArgs& a, const ElemArgs& e, uint32_t S, hipStream_t st) {
+template <int DS, int SIDE, int TILES = 0>
+hipError_t run_move(const PassArgs& a, const ElemArgs& e, uint32_t S, hipStream_t st) {
     switch (S) {
-    case 1: return run_pass<DS, PT_MOVE, 1, SIDE>(a, e, st);
-    case 3: return run_pass<DS, PT_MOVE, 3, SIDE>(a, e, st);
-    case 4: return run_pass<DS, PT_MOVE, 4, SIDE>(a, e, st);
-    case 5: return run_pass<DS, PT_MOVE, 5, SIDE>(a, e, st);
-    default: return run_pass<DS, PT_MOVE, 6, SIDE>(a, e, st);
+    case 1: return run_pass<DS, PT_MOVE, 1, SIDE, TILES>(a, e, st);
+    case 3: return run_pass<DS, PT_MOVE, 3, SIDE, TILES>(a, e, st);
+    case 4: return run_pass<DS, PT_MOVE, 4, SIDE, TILES>(a, e, st);
+    case 5: return run_pass<DS, PT_MOVE, 5, SIDE, TILES>(a, e, st);
+    default: return run_pass<DS, PT_MOVE, 6, SIDE, TILES>(a, e, st);
     }
 }
 
@@ -534,33 +577,30 @@ hipError_t sgd_group_tiles_fused(const GroupArgs& g, uint32_t* tile_lo, hipStrea
         e.out = g.out;
         return run_gather<PS_NONE>(a, e, g.W, stream);
     }
-    // LSD: the low tile bits carrying the tile id as a u16 code, then the high bits (the codes follow the
-    // elements), then the tile starts from the sorted codes
+    // LSD: the low tile bits, each element's high tile bits (<= 8: at most 65,535 tiles) written beside it as the
+    // second pass's digit; then the high bits, whose scatter also writes the tile starts
     const uint32_t b1 = tb / 2, b2 = tb - b1;
     a.dbits = b1;
     a.ndig = 1u << b1;
-    a.cshift = tbits;
-    a.cmask = 0xffffu;
+    a.sshift = tbits + b1;
     a.side_out = g.s.keys[0];
     a.lo = g.s.lo[0];
     e.out = g.s.el[0];
-    if (hipError_t x = run_gather<PS_CODE>(a, e, g.W, stream)) return x;
+    if (hipError_t x = run_gather<PS_DIG>(a, e, g.W, stream)) return x;
     PassArgs b = base_args(g.n, g.s);
     b.n_dev = g.s.lo[0] + a.ndig;
-    b.shift = b1;
     b.dbits = b2;
     b.ndig = ((nt - 1) >> b1) + 1;
     b.keys = g.s.keys[0];
-    b.cmask = 0xffffu;
-    b.side_out = g.s.keys[1];
     b.lo = g.s.lo[1];
+    b.bbits = b1;
+    b.blo = g.s.lo[0];
+    b.tile_lo = tile_lo;
+    b.n_tiles = nt;
     ElemArgs f{};
     f.in = g.s.el[0];
     f.out = g.out;
-    if (hipError_t x = run_move<PD_U16, PS_CODE>(b, f, g.W + 2, stream)) return x;
-    hipLaunchKernelGGL(k_tile_bounds, dim3((g.n + 1 + 2047) / 2048), dim3(256), 0, stream, (const uint16_t*)g.s.keys[1],
-                       (const uint32_t*)(g.s.lo[1] + b.ndig), nt, tile_lo);
-    return hipGetLastError();
+    return run_move<PD_U8, PS_NONE, 1>(b, f, g.W + 2, stream);
 }
 
 hipError_t sgd_group_sorted(const GroupArgs& g, hipStream_t stream) {

@@ -279,6 +279,19 @@ int main(int argc, char** argv) {
     test_fused("fused tile pass, C2 (uniform)", 1u << 24, 1u << 20, 0, scratch);
     test_fused("fused tile pass, C2 (Zipf 1.1)", 1u << 24, 1u << 20, 1, scratch);
     test_fused("fused tile pass, small", 100000, 3000, 0, scratch);
+    // two passes with the tile starts from the second one: every boundary in one or two chunks, a boundary on a
+    // chunk's edge, a tile count that is no multiple of the first pass's digits
+    test_fused("fused tile pass, sparse", 3000, 1u << 20, 0, scratch);
+    test_fused("fused tile pass, sparse Zipf", 5000, 1u << 20, 1, scratch);
+    test_fused("fused tile pass, one chunk", 2048, 1u << 17, 0, scratch);
+    test_fused("fused tile pass, one chunk + 1", 2049, 1u << 17, 0, scratch);
+    test_fused("fused tile pass, one chunk - 1", 2047, 1u << 17, 0, scratch);
+    test_fused("fused tile pass, 257 tiles", 70000, 65536 + 256, 0, scratch);
+    test_fused("fused tile pass, 4096 tiles, one key in the last", 1u << 20, (1u << 20) - 255, 0, scratch);
+    if (argc > 1 && !strcmp(argv[1], "fused")) {  // the fused tile pass only
+        printf("%s (%d failures)\n", failures ? "FAILED" : "ALL OK", failures);
+        return failures ? 1 : 0;
+    }
     test_group("sorted W=1, C2 size", 1u << 24, 1u << 20, 0, false, false, 1, scratch);
     test_group("sorted W=1, C3 size, bad keys + nulls", 1u << 22, 1u << 20, 0, true, true, 1, scratch);
     test_group("sorted W=1, bad keys (no drop)", 1u << 20, 1u << 20, 0, true, false, 1, scratch);
