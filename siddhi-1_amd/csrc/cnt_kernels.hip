@@ -2,6 +2,10 @@
 //
 //     every e1=S[f0]<m:n>, e2=S[fA] or e3=S[fB] [within W]          (SEQUENCE, partitioned, 1 <= m, n <= CNT_R)
 //
+// and its single-tail form, one stream state in place of the logical pair (gen_engine.h cntTail),
+//
+//     every e1=S[f0]<m:n>, e2=S[f1] [within W]
+//
 // (BASELINE configs[2], "C3" / "C3_min1").  The general kernel (gen_kernels.hip) runs this query through the
 // processor graph with every StateEvent / StreamEvent in the key-interleaved pools of HBM: a count partial
 // that grows by one event costs ~25 word accesses to distinct rows (pool bitmaps, records, list entries,
@@ -30,6 +34,9 @@
 //       the event appended to the chain, removed again when the filter fails; SEQUENCE drops a failed one)
 //   CountPostStateProcessor.java:39-66 (SEQUENCE: n >= m -> next state's addState; n != max -> own addState;
 //       n == max -> stateChanged)
+//   the single tail: StreamPreStateProcessor.java:287-323 (reset / update of its one list), :364-403 processAndReturn
+//       (the event fills e2; a failed filter clears it and SEQUENCE drops the partial), StreamPostStateProcessor.java:
+//       64-83 (the match's timestamp, the event returned)
 #include <hip/hip_runtime.h>
 
 #include "../../include/siddhi_gpu.h"
@@ -41,7 +48,8 @@
 
 namespace {
 
-template <int NW> struct CntKey {
+// PROJ: a match's select list is evaluated by the lane that emits it (project(), the `_p` kernels)
+template <int NW, bool PROJ = false> struct CntKey {
     const cGenProgram& G;
     const GenArgs& A;
     gu32* S;
@@ -92,6 +100,9 @@ template <int NW> struct CntKey {
         W(w_) = (uint32_t)(uint64_t)v;
         W(w_ + 1) = (uint32_t)((uint64_t)v >> 32);
     }
+    // the lists after the count state that hold X while `inL`: the logical pair's two, or the single tail's one
+    // (G.cntTail: pB = pA, so every read and write of pB's words below is pA's again)
+    __device__ __forceinline__ uint32_t nextLists() const { return G.cntTail ? 1u : 2u; }
     __device__ __forceinline__ uint32_t stw(uint32_t se, uint32_t f) const { return G.offST + se * G.stWords + f; }
     __device__ __forceinline__ uint32_t sew(uint32_t e, uint32_t f) const { return G.offSE + e * G.seWords + f; }
 
@@ -99,7 +110,7 @@ template <int NW> struct CntKey {
     // seedN << 7 | f0 << 8 | fA << 16 | fB << 24, the partial's ts, then per chain event seq, ts, null bits, words
     __device__ __forceinline__ gu32& RW(uint32_t w_) const { return R[(size_t)w_ * K + k]; }
     __device__ __forceinline__ uint32_t rev(uint32_t j, uint32_t f) const { return GEN_REC_EV + j * (5u + NW) + f; }
-    __device__ void loadRec() {
+    __device__ __forceinline__ void loadRec() {
         const uint32_t h = RW(0);
         xts = (int64_t)((uint64_t)RW(1) | ((uint64_t)RW(2) << 32));
         n = h & 15u;
@@ -130,7 +141,7 @@ template <int NW> struct CntKey {
     }
     // the header, the timestamp and the chain events appended since the load (a chain only grows at its end
     // or restarts: the events below `dirty` are the record's already)
-    __device__ void storeRec() const {
+    __device__ __forceinline__ void storeRec() const {
         if (!wasRec) W(0) = 1u | GEN_W0_REG;
         RW(0) = n | (inP0p ? 16u : 0u) | (inP0n ? 32u : 0u) | (inL ? 64u : 0u) | (seedN ? 128u : 0u) | (f0 << 8) |
                 (fA << 16) | (fB << 24);
@@ -152,7 +163,7 @@ template <int NW> struct CntKey {
 
     // ---- load: false = the stored lists are not of this kernel's canonical shape (the general kernel
     // takes the key's run)
-    __device__ bool load() {
+    __device__ __forceinline__ bool load() {
         const uint32_t w0 = W(0);
         if (w0 & GEN_W0_REG) {
             loadRec();
@@ -200,7 +211,7 @@ template <int NW> struct CntKey {
         seedN = sd;
         if (xi == GEN_NIL) return true;
         if (xi >= G.STCAP) return false;
-        const uint32_t rc = (inP0p ? 1u : 0u) + (inP0n ? 1u : 0u) + (inL ? 2u : 0u);
+        const uint32_t rc = (inP0p ? 1u : 0u) + (inP0n ? 1u : 0u) + (inL ? nextLists() : 0u);
         if (W(stw(xi, ST_TYPE)) != 0u || W(stw(xi, ST_RC)) != rc) return false;
         if (W(stw(xi, ST_SLOTS + (uint32_t)sA)) != GEN_NIL || W(stw(xi, ST_SLOTS + (uint32_t)sB)) != GEN_NIL) return false;
         xts = R64(stw(xi, ST_TS));
@@ -240,11 +251,11 @@ template <int NW> struct CntKey {
     }
 
     // ---- store: the lists in the canonical layout, free bitmaps rebuilt
-    __device__ void store() const {
+    __device__ __forceinline__ void store() const {
         W(0) = 1u;
         W(ks0 + KS_FLAGS) = f0;
-        W(ksA + KS_FLAGS) = fA;
         W(ksB + KS_FLAGS) = fB;
+        W(ksA + KS_FLAGS) = fA;   // (the single tail: pB is pA, whose flag word fA is)
         const bool x = n > 0u;
         const uint32_t seedIdx = x ? 1u : 0u;
         W(ks0 + KS_PLEN) = (x && inP0p) ? 1u : 0u;
@@ -264,7 +275,7 @@ template <int NW> struct CntKey {
             const uint32_t b = G.offST;
             W64(b + ST_TS, xts);
             W(b + ST_TYPE) = 0u;
-            W(b + ST_RC) = (inP0p ? 1u : 0u) + (inP0n ? 1u : 0u) + (inL ? 2u : 0u);
+            W(b + ST_RC) = (inP0p ? 1u : 0u) + (inP0n ? 1u : 0u) + (inL ? nextLists() : 0u);
             for (int s = 0; s < G.nslots; s++) W(b + ST_SLOTS + (uint32_t)s) = s == s0 ? 0u : GEN_NIL;
 #pragma unroll
             for (int j = 0; j < CNT_R; ++j) {
@@ -339,7 +350,9 @@ template <int NW> struct CntKey {
     }
     // filter of processor p on X: slot s0 = the chain [0, len), slots `evSlot` and `evSlot2` (the AND pair's
     // partner slot, already filled by this event; -1: none) = the event alone
-    __device__ bool evalOn(int p, uint32_t len, int evSlot, const AbsEv<NW>& ev, int evSlot2 = -1) {
+    // (always inlined: with the select list's copy of the interpreter in the kernel the inliner leaves a call of this
+    // behind, and a call that takes the key object's address keeps the whole object in scratch, 1.1 KB per lane)
+    __device__ __forceinline__ bool evalOn(int p, uint32_t len, int evSlot, const AbsEv<NW>& ev, int evSlot2 = -1) {
         const auto& P = G.pre[p];
         if (P.flen == 0) return true;
         auto var_ = [&](uint32_t s, uint32_t a, int32_t c) -> GVal {
@@ -362,7 +375,7 @@ template <int NW> struct CntKey {
 
     // ---- a match (QuerySelector input): X with e1's chain and the event in `evSlot` (and, for the AND pair, in
     // `evSlot2` too) (Lane::project's record)
-    __device__ void project(const AbsEv<NW>& ev, uint32_t pos, int evSlot, int evSlot2 = -1) {
+    __device__ __forceinline__ void project(const AbsEv<NW>& ev, uint32_t pos, int evSlot, int evSlot2 = -1) {
         // one raw slot per match, reserved at once for the lanes of the wave that match here (one atomic per wave
         // and call site; per-lane chunks left ~2.5 unused slots per matching key, each marked empty by a
         // scattered store)
@@ -404,10 +417,40 @@ template <int NW> struct CntKey {
         }
         gp(A.o.t_cnt)[pos] += 1;
         if (A.mode & GEN_M_TFIRST) gp(A.o.t_first)[pos] = (uint32_t)r;
+        // PROJ: the select list and `having`, as gen_kernels.hip projectSelect lays them out (3 words per item: value lo,
+        // hi, null).  Everything an item reads is in the lane: e1's chain (any index: chainIdx), the trigger in evSlot /
+        // evSlot2; a slot the match does not hold is null; `having` reads the items just written (SG_PROJ_SLOT_OUT).  No
+        // aggregators, every item at most two entries deep (gen_host.hip proj_in_lane).  A run-time loop over the
+        // items: one more inlined copy of the interpreter, not one per item.
+        if constexpr (PROJ) {
+            gu32* pv = rec + G.projOff;
+            for (uint32_t i = G.projAgg; i < G.projN; i++) {
+                const GVal v = jo_eval<false>(G.code, G.projPc[i], G.projLen[i], err,
+                                              [&](uint32_t s, uint32_t a, int32_t c) -> GVal {
+                        if (s == SG_PROJ_SLOT_OUT)
+                            return GVal{(uint64_t)pv[3 * a] | ((uint64_t)pv[3 * a + 1] << 32), pv[3 * a + 2] != 0};
+                        if ((int)s == s0) {
+                            const int j = chainIdx(c, n);
+                            return j < 0 ? GVal{0, true} : chainAttr(j, a);
+                        }
+                        if (((int)s == evSlot || (int)s == evSlot2) && chainIdx(c, 1u) == 0) return word(ev.w, ev.nb, a);
+                        return GVal{0, true};
+                    },
+                                              [&](uint32_t s, int32_t c) -> bool {
+                        if ((int)s == s0) return chainIdx(c, n) < 0;
+                        if ((int)s == evSlot || (int)s == evSlot2) return chainIdx(c, 1u) != 0;
+                        return true;
+                    });
+                const uint32_t o = 3u * (i - G.projAgg);
+                pv[o] = (uint32_t)v.b;
+                pv[o + 1] = (uint32_t)(v.b >> 32);
+                pv[o + 2] = v.null ? 1u : 0u;
+            }
+        }
     }
 
     // ---- one event of this key (SequenceMultiProcessStreamReceiver: stabilize, then pA, pB, p0)
-    __device__ void event(const AbsEv<NW>& ev, uint32_t pos) {
+    __device__ __forceinline__ void event(const AbsEv<NW>& ev, uint32_t pos) {
         trigRank = 0;
         // expireEvents over p0, pA, pB: X expires as a whole (one isExpired per StateEvent); found in p0's
         // lists first, it is cloned into p0.newAndEvery by withinEvery and promoted — a clone the reset below
@@ -439,15 +482,18 @@ template <int NW> struct CntKey {
         // when both passed.  Either way X leaves both lists, and a filled slot makes the count state drop it
         // below — so an AND match needs fA and fB on the same event.  (One call site per filter and one for the
         // match: each inlined evaluation carries the interpreter, and more copies put the key object in scratch.)
+        // The single tail (G.cntTail; StreamPreStateProcessor.java:364-403, StreamPostStateProcessor.java:64-83): pA is a
+        // plain stream state and there is no pB — one pending entry scanned, a pass matches with e2 filled, a failed
+        // filter clears the slot again and SEQUENCE drops X from the pending list.
         bool matched = false;
         if (xL) {
-            const bool both = G.cntAnd != 0;
-            scanned += 2;
+            const bool both = G.cntAnd != 0, tail = G.cntTail != 0;
+            scanned += tail ? 1u : 2u;
             fA &= ~(uint32_t)GF_CHANGED;
             const bool a = evalOn(pA, n, sA, ev);
             if (a) fA |= GF_CHANGED;
             bool bp = false;
-            if (both || !a) {
+            if (!tail && (both || !a)) {
                 fB &= ~(uint32_t)GF_CHANGED;
                 bp = evalOn(pB, n, sB, ev, (both && a) ? sA : -1);
                 if (bp) fB |= GF_CHANGED;
@@ -658,14 +704,14 @@ extern "C" __global__ void __launch_bounds__(256) k_cnt_split(const GenArgs a) {
 }
 
 // ---- batch: one lane per key walks its events of the key-sorted batch ----
-template <int NW> __device__ void cnt_batch(const GenArgs& a) {
+template <int NW, bool PROJ> __device__ __forceinline__ void cnt_batch(const GenArgs& a) {
     const uint32_t key = blockIdx.x * 64u + threadIdx.x;
     uint32_t b = 0, e = 0;
     if (key < a.K) {
         b = gp(a.b.seg_begin)[key];
         e = gp(a.b.seg_end)[key];
     }
-    CntKey<NW> L(a, key < a.K ? key : 0u);
+    CntKey<NW, PROJ> L(a, key < a.K ? key : 0u);
     bool walk = b < e;
     bool fb = false;
     if (walk && !L.load()) {  // not this kernel's canonical state: the general kernel walks the whole run
@@ -687,7 +733,7 @@ template <int NW> __device__ void cnt_batch(const GenArgs& a) {
                 pos = a.b.sidx ? gp(a.b.sidx)[i] : i;
                 ev.ts = gp(a.b.ts)[pos];
                 ev.seq = a.b.seq_base + pos;
-                abs_gather<NW>(a, *(cGenProgram*)a.G, pos, ev);
+                [[clang::always_inline]] abs_gather<NW>(a, *(cGenProgram*)a.G, pos, ev);
             }
             L.event(ev, pos);
         }
@@ -695,8 +741,9 @@ template <int NW> __device__ void cnt_batch(const GenArgs& a) {
         else L.store();
         ky = 1;
     }
-    abs_fallback(a, fb, key, b);
-    abs_wave_stats(a, L.scanned, L.created, L.matches, ky, L.err, fb ? 1ull : 0ull);
+    // (inlined here: a call that takes the kernel arguments' address copies all 672 B of them to scratch)
+    [[clang::always_inline]] abs_fallback(a, fb, key, b);
+    [[clang::always_inline]] abs_wave_stats(a, L.scanned, L.created, L.matches, ky, L.err, fb ? 1ull : 0ull);
 }
 
 // ---- the records written back to the blocks in the canonical layout (before a snapshot, min-seq scan, ...) ----
@@ -719,9 +766,17 @@ template <int NW> __device__ void cnt_flush(const GenArgs& a) {
 #define SG_CNT_WAVES 4
 #endif
 #define CNT_OCC(NW) __attribute__((amdgpu_waves_per_eu((NW) <= 3 ? SG_CNT_WAVES : 1, 8)))   // (wider events: no floor)
+// The `_p` kernels (the select list projected in the lane): their own floor for NW <= 3 (DESIGN §5c has both builds)
+#ifndef SG_CNT_WAVES_P
+#define SG_CNT_WAVES_P 4
+#endif
+#define CNT_OCC_P(NW) __attribute__((amdgpu_waves_per_eu((NW) <= 3 ? SG_CNT_WAVES_P : 1, 8)))
 #define CNT_KERNELS(NW)                                                                                             \
     extern "C" __global__ void __launch_bounds__(64) CNT_OCC(NW) k_cnt_batch_##NW(const GenArgs ap) {   \
-        cnt_batch<NW>(ap);                                                                                         \
+        cnt_batch<NW, false>(ap);                                                                                  \
+    }                                                                                                              \
+    extern "C" __global__ void __launch_bounds__(64) CNT_OCC_P(NW) k_cnt_batch_##NW##_p(const GenArgs ap) {        \
+        cnt_batch<NW, true>(ap);                                                                                   \
     }                                                                                                              \
     extern "C" __global__ void __launch_bounds__(64) k_cnt_flush_##NW(const GenArgs ap) { cnt_flush<NW>(ap); }
 CNT_KERNELS(1)

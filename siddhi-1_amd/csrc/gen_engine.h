@@ -191,7 +191,12 @@ struct GenProgram {
     // them (the receiver's reverse order), cntWE: p0's withinEvery is p0 itself (an expired partial of p0's
     // lists is cloned into it, StreamPreStateProcessor.java:354-357); absNW / absOff give the word layout
     int32_t cntOk, cntP0, cntPA, cntPB, cntWE;
-    int32_t cntAnd, cntPad;   // the pair is a logical AND (`e2=S[fA] and e3=S[fB]`) instead of an OR
+    int32_t cntAnd;    // the pair is a logical AND (`e2=S[fA] and e3=S[fB]`) instead of an OR
+    // cntTail: the single-tail wiring `every e1=S[f0]<m:n>, e2=S[f1] [within W]` — two processors and two slots, cntPA
+    // the stream state after the count (one pending / newAndEvery list and one flag word; cntPB is unused).
+    // cntProj: the select list set by sg_set_projection is one k_cnt_batch_<NW>_p evaluates in the lane that emits the
+    // match, from the chain and the trigger event in its registers (the rule of seqProj)
+    int32_t cntTail, cntProj, cntPad;
     uint32_t absWordAt[ABS_MAXNW];  // the StreamEvent record word (SE_ATTR + ...) of each captured word
     // the chained stream states `[every] e1=S[f0] -> e2=S[f1] -> ... -> en=S[f(n-1)] [within W]` (PATTERN,
     // partitioned, one stream, 2 <= n <= CHN_MAXN), which run on the register-window kernel of chn_kernels.hip

@@ -58,6 +58,7 @@ GK_TABLE(kAbsdTimers, GK_NW8, k_absd_timers_, )
 GK_TABLE(kAbsdTimersF, GK_NW8, k_absd_timersf_, )
 GK_TABLE(kAbsdFlush, GK_NW8, k_absd_flush_, )
 GK_TABLE(kCntBatch, GK_NW8, k_cnt_batch_, )
+GK_TABLE(kCntBatchP, GK_NW8, k_cnt_batch_, _p)
 GK_TABLE(kCntFlush, GK_NW8, k_cnt_flush_, )
 GK_TABLE(kChnBatch, GK_CHN, k_chn_batch_, )   // [1 + 3 * kept words + (states - 2)]
 GK_TABLE(kChnWide, GK_CHN, k_chn_wide_, )     // (over the keys the chain kernel handed over)
@@ -358,13 +359,47 @@ bool reg_layout(GenProgram& G) {
 //     every e1=S[f0]<m:n>, e2=S[fA] or e3=S[fB] [within W]      (SEQUENCE, partitioned, one stream)
 // with the processors wired as StateInputStreamParser wires that query (a count state inside `every`, its
 // post processor feeding a logical OR pair whose post processors reach the selector); 1 <= m, n <= CNT_R.
+// and the single-tail wiring of the same kernel
+//     every e1=S[f0]<m:n>, e2=S[f1] [within W]
+// (two processors: the count state's post processor feeding one stream state whose post processor reaches the selector).
 // Anything else stays on the general kernels.
+void cnt_tail_shape(GenProgram& G) {
+    if (G.nprocs != 2 || G.nslots != 2) return;
+    const GenRecv& R = G.recv[0];
+    if (R.n != 2 || R.nStateProcs != 2) return;
+    const int p0 = R.procs[0], p1 = R.procs[1];  // an event visits procs[1], [0]
+    const GenPre &P0 = G.pre[p0], &P1 = G.pre[p1];
+    const GenPost &Q0 = G.post[p0], &Q1 = G.post[p1];
+    if (P0.kind != GK_COUNT || P0.absent || !P0.isStart || P0.minCount < 1 || P0.maxCount > CNT_R ||
+        P0.minCount > P0.maxCount || P0.countPost != p0)
+        return;
+    if (P1.kind != GK_STREAM || P1.absent || P1.isStart) return;
+    if (Q0.nextStatePre != p1 || Q0.nextEveryStatePre != p0 || Q0.callbackPre != GEN_NONE || Q0.hasNext) return;
+    if (Q1.nextStatePre != GEN_NONE || Q1.nextEveryStatePre != GEN_NONE || Q1.callbackPre != GEN_NONE || !Q1.hasNext)
+        return;
+    if (P1.withinEvery != GEN_NONE || (P0.withinEvery != GEN_NONE && P0.withinEvery != p0)) return;
+    if (G.nAll != 2 || G.allProcs[0] != p0) return;
+    if (G.within != -1 && (G.nStartIds != 1 || G.startIds[0] != P0.stateId)) return;
+    if (G.slotStream[P0.stateId] != 0 || G.slotStream[P1.stateId] != 0) return;
+    // CountPreStateProcessor drops a partial once slot stateId + 1 is filled (:97-103): the tail's slot
+    if (P1.stateId != P0.stateId + 1) return;
+    if ((uint32_t)P0.maxCount > G.MC) return;
+    if (!shallow(G, P0) || !shallow(G, P1) || !reg_layout(G)) return;
+    G.cntP0 = p0;
+    G.cntPA = p1;
+    G.cntPB = p1;   // (unused: the kernel's second list and flag word are the first again)
+    G.cntWE = P0.withinEvery == p0 ? 1 : 0;
+    G.cntTail = 1;
+    G.cntOk = getenv("SG_NO_CNT") ? 0 : 1;
+}
+
 void cnt_shape(GenProgram& G) {
     G.cntOk = 0;
     G.cntAnd = 0;
-    if (G.qtype != SG_Q_SEQUENCE || !G.partitioned || G.nstreams != 1 || G.nprocs != 3 || G.nslots != 3 ||
-        G.nStartup != 0)
-        return;
+    G.cntTail = G.cntProj = 0;
+    if (G.qtype != SG_Q_SEQUENCE || !G.partitioned || G.nstreams != 1 || G.nStartup != 0) return;
+    if (G.nprocs == 2) return cnt_tail_shape(G);
+    if (G.nprocs != 3 || G.nslots != 3) return;
     const GenRecv& R = G.recv[0];
     if (R.n != 3 || R.nStateProcs != 3) return;
     const int p0 = R.procs[0], pA = R.procs[2], pB = R.procs[1];  // an event visits procs[2], [1], [0]
@@ -1080,8 +1115,8 @@ __global__ void k_gen_live(const GenProgram* G, const uint32_t* S, uint32_t K, u
         const uint32_t h = rec[(size_t)((G->seqOk && (w0 & GEN_W0_SEQP)) ? seq_rec_rows(G->absNW, G->seqN) : 0u) * K + k];
         if (G->seqOk)   // the sequence's carry: a partial per set liveness bit
             live = (unsigned long long)__popc((h >> 4) & 7u);
-        else if (G->cntOk)   // the count partial: one StateEvent in each list it is in
-            live = (h & 15u) ? ((h >> 4) & 1u) + ((h >> 5) & 1u) + 2u * ((h >> 6) & 1u) : 0u;
+        else if (G->cntOk)   // the count partial: one StateEvent in each list it is in (the pair's two, or the tail's one)
+            live = (h & 15u) ? ((h >> 4) & 1u) + ((h >> 5) & 1u) + (G->cntTail ? 1u : 2u) * ((h >> 6) & 1u) : 0u;
         else            // the absent shape: each partial holds its e1 (the seed holds no event)
             live = h & 15u;
         if (live) atomicAdd(out, live);
@@ -1739,8 +1774,8 @@ static GenRoute gen_route(const GenEngine* e) {
     const GenK genBatch{k_gen_batch, "k_gen_batch"}, genTimers{k_gen_timers, "k_gen_timers"};
     GenRoute r;
     // (a specialised kernel evaluates no device projection, except the select list the stencil kernels evaluate from
-    // the match's window and the chain kernels from wherever the match's events are; the key ids of the partitioned
-    // stencil kernel fit its element tags)
+    // the match's window, the chain kernels from wherever the match's events are and the count kernel from the chain in
+    // its registers; the key ids of the partitioned stencil kernel fit its element tags)
     const bool seq = G.seqOk && (noProj || G.seqProj) && e->fb_list && e->rec && e->ekey;
     if (G.absOk && noProj && e->fb_list && e->tstage && e->keyorder) {
         // the register-window kernel; the deep keys it hands over, one wave each (SG_NO_ABSD: none; their LDS slice
@@ -1766,11 +1801,13 @@ static GenRoute gen_route(const GenEngine* e) {
         }
         r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST, h));
         r.adv.push_back(stage(genTimers, "keys handed over", byList, GEN_M_NOPAIRS, h));
-    } else if (G.cntOk && noProj && e->fb_list) {
-        // the register-window kernel, then the general kernel over the keys it handed over (whole runs); this shape
-        // emits at most one match per event
+    } else if (G.cntOk && (noProj || G.cntProj) && e->fb_list) {
+        // the register-window kernel, then the general kernel over the keys it handed over (whole runs, projecting its
+        // own matches); this shape emits at most one match per event
         r.family = GEN_F_CNT;
-        r.push.push_back(stage(kCntBatch[NW], "register window, lane per key", byKeys, GEN_M_TFIRST, 0, true));
+        r.push.push_back(stage((noProj ? kCntBatch : kCntBatchP)[NW],
+                               noProj ? "register window, lane per key" : "register window, lane per key, select list projected",
+                               byKeys, GEN_M_TFIRST, 0, true));
         r.push.push_back(stage(genBatch, "keys handed over", byList, GEN_M_KEYLIST | GEN_M_TFIRST, 1));
     } else if (seq && !G.seqFlat && e->K < SEQ_KEYMASK) {
         // one lane per key (adopt / hand over, the element tags), the stencil kernel (one thread per element with an
@@ -2281,7 +2318,7 @@ int gen_poll(GenEngine* e, uint32_t mem, sg_match_batch* out, std::string& msg) 
     return SG_OK;
 }
 
-// a projection the sequence and chain kernels evaluate in the thread that emits the match: no aggregators, every
+// a projection the sequence, chain and count kernels evaluate in the thread that emits the match: no aggregators, every
 // item at most two entries deep and without ifThenElse (jo_eval<false>, as seq_terms asks of the filters), reading the
 // stream's own attributes
 static bool proj_in_lane(const GenProgram& G) {
@@ -2355,6 +2392,7 @@ int gen_set_projection(GenEngine* e, const uint32_t* code, uint32_t words, const
     const bool inLane = proj_in_lane(G);
     G.seqProj = G.seqOk && inLane;
     G.chnProj = G.chnOk && inLane;
+    G.cntProj = G.cntOk && inLane;
     G.projOff = e->recWords;
     e->recWords += 3 * (S + H);
     if (A) {  // the aggregators' per-key state joins the key blocks (no push yet: all zero)
